@@ -31,6 +31,7 @@ LIBS = {
     "libtransoar_attn.so": ["attn.hip"],
     "libtransoar_optim.so": ["optim.hip"],
     "libtransoar_criterion.so": ["criterion.hip"],
+    "libtransoar_segproxy.so": ["seg_proxy.hip"],
 }
 
 

@@ -80,6 +80,11 @@ class TransoarCriterion(nn.Module):
         return torch.where(hit, l1, zero).sum() / denom, torch.where(hit, one_minus_giou, zero).sum() / denom
 
     def loss_segmentation(self, outputs, targets):
+        from . import seg_proxy
+        if seg_proxy.losses_usable(outputs["pred_seg"], targets):
+            # one pass over the logits each way (csrc/seg_proxy.hip); the code below is what it computes
+            return seg_proxy.seg_losses(outputs["pred_seg"], targets, self._seg_fg_bg, self._dice_loss.smooth_nom,
+                                        self._dice_loss.smooth_denom)
         if self._seg_fg_bg:
             targets = (targets > 0).to(targets.dtype)
         targets = targets.squeeze(1).long()
@@ -91,7 +96,7 @@ class TransoarCriterion(nn.Module):
         from . import fused_criterion
         if fused_criterion.usable(self, outputs, targets, seg_targets):
             # one forward and one backward launch (csrc/criterion.hip) instead of ~270 tiny ones; the code below is what it computes
-            return fused_criterion.run(self, outputs, targets, anchors)
+            return fused_criterion.run(self, outputs, targets, anchors, seg_targets)
         num_boxes = targets.num_boxes
         n_valid = None
         if targets.n_present is not None:

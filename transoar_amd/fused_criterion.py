@@ -1,11 +1,12 @@
 """The set criterion of the training step as ONE forward and ONE backward launch (include/transoar_criterion.h,
 csrc/criterion.hip): matcher geometry, one assignment per decoder output, L1 / GIoU on the matched boxes and the BCE on
-the soft labels -- transoar/models/criterion.py:9-125 with matcher.py:9-65 in its anchor-matching form.
+the soft labels -- transoar/models/criterion.py:9-125 with matcher.py:9-65 in its anchor-matching form.  With the
+segmentation proxy on, segce / segdice come from the seg-proxy kernels (seg_proxy.py) into the same loss vector.
 
 transoar_amd/criterion.py (the torch mirror, ~270 launches of ~5 us per step with its autograd graph) stays the path for
-everything this kernel does not cover -- CPU tensors, predicted-box matching, one query per class, the segmentation
-proxy losses -- and is what the GPU tests compare this kernel with (tests/test_criterion_gpu.py), next to the goldens
-generated from the reference (g7, g10, g11 run through here).  TRANSOAR_FUSED_CRITERION=0 switches it off.
+everything this kernel does not cover -- CPU tensors, predicted-box matching, one query per class, segmentation proxy
+inputs the seg-proxy kernels do not take -- and is what the GPU tests compare this kernel with (tests/test_criterion_gpu.py),
+next to the goldens generated from the reference (g7, g10, g11 run through here).  TRANSOAR_FUSED_CRITERION=0 switches it off.
 """
 import ctypes
 import os
@@ -13,6 +14,7 @@ import os
 import torch
 
 from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import seg_proxy
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_criterion.so")
 if not os.path.exists(_LIB_PATH):
@@ -53,7 +55,9 @@ def usable(criterion, outputs, targets, seg_targets):
     if not (ENABLED and torch.is_tensor(logits) and logits.is_cuda and torch.is_tensor(boxes) and boxes.is_cuda):
         return False
     m = criterion.matcher
-    if criterion._seg_proxy or not m.anchor_matching or m.num_organs != criterion.num_classes:
+    if not m.anchor_matching or m.num_organs != criterion.num_classes:
+        return False
+    if criterion._seg_proxy and not seg_proxy.losses_usable(outputs.get("pred_seg"), seg_targets):
         return False
     aux = outputs.get("aux_outputs", [])
     n, q = logits.shape[0], logits.shape[1]
@@ -121,13 +125,19 @@ class _SetCriterion(torch.autograd.Function):
         return grad_logits, grad_boxes, None, None, None, None, None, None, None, None
 
 
-def run(criterion, outputs, targets, anchors):
+def run(criterion, outputs, targets, anchors, seg_targets=None):
     """-> LossDict with the keys and the order of TransoarCriterion.forward (criterion.py); .vector holds them as one tensor."""
     aux = outputs.get("aux_outputs", [])
     m = criterion.matcher
     losses = _SetCriterion.apply(outputs["pred_logits"], outputs["pred_boxes"], tuple(a["pred_logits"] for a in aux), anchors,
                                     targets.boxes, targets.present, targets.num_boxes, targets.n_present,
                                     (m.cost_class, m.cost_bbox, m.cost_giou), criterion.num_classes)
+    if criterion._seg_proxy:
+        # the set kernel leaves zeros in the segce / segdice slots: the seg-proxy losses take their place (one concatenation;
+        # both stay differentiable, so TrainStep._weighted_total weights them)
+        dice = criterion._dice_loss
+        seg = seg_proxy.seg_loss_vector(outputs["pred_seg"], seg_targets, criterion._seg_fg_bg, dice.smooth_nom, dice.smooth_denom)
+        losses = torch.cat((losses[:3], seg.to(losses.dtype), losses[5:]))
     # the kernel writes the vector in the dict's order: bbox, giou, cls, segce, segdice, then (bbox_i, giou_i, cls_i) per auxiliary output
     keys = ["bbox", "giou", "cls", "segce", "segdice"]
     for i in range(len(aux)):

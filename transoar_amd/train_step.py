@@ -66,6 +66,7 @@ class TrainStep:
         self._replay_done = None
         self._static_counts = None
         self._static_counts_local = None
+        self._static_seg = None
         self._expect_total = None
         self._want_graph = graph
         self.num_classes = config["num_classes"]
@@ -165,18 +166,21 @@ class TrainStep:
     # 60 ms of GPU work), so forward + criterion + backward are captured once into a HIP graph over static
     # input buffers and replayed; the gradient exchange (eager, on the flat buckets, after the
     # replay -- no collective inside the graph) and the fused optimizer follow.
-    def capture(self, data, targets, warmup=3):
+    def capture(self, data, targets, seg_targets=None, warmup=3):
         """Capture fwd+loss+bwd for inputs of this shape.  Raises if anything in the step cannot be
-        captured; the caller may then keep using the eager step."""
+        captured; the caller may then keep using the eager step.  With the segmentation proxy loss on, seg_targets
+        (the label volume) is required: it is copied into a static buffer that every replay refills."""
         assert self._want_graph, "construct TrainStep(graph=True)"
         if not isinstance(targets, DenseTargets):
             targets = DenseTargets.from_list(targets, self.num_classes, data.device)
         self.model.train()
         self._static_x = data.clone()
         self._static_t = DenseTargets(targets.boxes.clone(), targets.present.clone(), targets.num_boxes)
+        self._static_seg = None
         if getattr(self.criterion, "_seg_proxy", False):
-            raise RuntimeError("TrainStep.capture: the segmentation proxy loss needs seg_targets, which the captured "
-                               "step does not carry; use the eager step for use_seg_proxy_loss configs")
+            if not torch.is_tensor(seg_targets):
+                raise RuntimeError("TrainStep.capture: the segmentation proxy loss is on; pass the label volume as seg_targets")
+            self._static_seg = seg_targets.to(data.device).clone(memory_format=torch.contiguous_format)
         # the loss normalisers (number of boxes, number of present classes) live in a static DEVICE buffer that
         # is refilled before every replay -- also on one GPU: a Python int would be baked into the captured
         # graph and mis-scale every batch whose box count differs from the captured one
@@ -200,7 +204,7 @@ class TrainStep:
         eager_total = None
         with torch.cuda.stream(side):
             for k in range(warmup):
-                total = self._eager_fwd_bwd(self._static_x, self._static_t)[0]
+                total = self._eager_fwd_bwd(self._static_x, self._static_t, self._static_seg)[0]
                 if k == 0:
                     eager_total = total          # the loss on the weights capture() was called with
                     if self.reducer.active:
@@ -243,7 +247,7 @@ class TrainStep:
                 if self._static_counts_local is not None:
                     self._static_counts.copy_(self._static_counts_local)
                     self.reducer.reduce_counts(self._static_counts)
-                self._static_total, self._static_losses = self._eager_fwd_bwd(self._static_x, self._static_t)
+                self._static_total, self._static_losses = self._eager_fwd_bwd(self._static_x, self._static_t, self._static_seg)
                 if self.capture_exchange:
                     self.reducer.exchange()       # buckets not launched by a hook yet, the joins, the widening copies
                 if self.capture_optimizer:
@@ -328,13 +332,23 @@ class TrainStep:
         return torch.stack((torch.as_tensor(float(targets.num_boxes), device=targets.boxes.device),
                             targets.present.sum().float()))
 
-    def _eager_fwd_bwd(self, data, targets):
+    def _eager_fwd_bwd(self, data, targets, seg_targets=None):
         self.reducer.begin()
-        total, losses = self.loss(data, targets, counts=getattr(self, "_static_counts", None))
+        total, losses = self.loss(data, targets, seg_targets, counts=getattr(self, "_static_counts", None))
         total.backward()
         return total.detach(), losses
 
-    def _replay(self, data, targets):
+    def _replay(self, data, targets, seg_targets=None):
+        if self._static_seg is not None:
+            # the labels are an input of the captured graph like the volume: copied in, never baked in
+            if not torch.is_tensor(seg_targets) or seg_targets.shape != self._static_seg.shape \
+                    or seg_targets.dtype != self._static_seg.dtype:
+                raise RuntimeError("TrainStep: the captured step (segmentation proxy loss on) needs seg_targets of shape %s and "
+                                   "dtype %s, got %s" % (tuple(self._static_seg.shape), self._static_seg.dtype,
+                                                         None if not torch.is_tensor(seg_targets) else
+                                                         "%s %s" % (tuple(seg_targets.shape), seg_targets.dtype)))
+            if seg_targets.data_ptr() != self._static_seg.data_ptr():
+                self._static_seg.copy_(seg_targets)
         if data.data_ptr() != self._static_x.data_ptr():
             self._static_x.copy_(data)
         if targets is not self._static_t:
@@ -370,6 +384,7 @@ class TrainStep:
         self._graph = None
         self._static_counts = None
         self._static_counts_local = None
+        self._static_seg = None
         self.reducer.overlap = True
 
     def _clip(self):
@@ -381,7 +396,7 @@ class TrainStep:
         if self._graph is not None:
             if not isinstance(targets, DenseTargets):
                 targets = DenseTargets.from_list(targets, self.num_classes, data.device)
-            return self._replay(data, targets)
+            return self._replay(data, targets, seg_targets)
         self.model.train()
         if self._want_graph and data.is_cuda:
             # an eager step of a TrainStep that will be captured runs on the capture's side stream: autograd's AccumulateGrad

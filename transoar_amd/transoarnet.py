@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import shadow
+from . import seg_proxy, shadow
 from .backbone import AttnFPN
 from .criterion import TransoarCriterion
 from .focused_decoder import FocusedDecoder
@@ -144,8 +144,12 @@ class TransoarNet(nn.Module):
             boxes = (boxes.tanh() * self._restrictions + self._anchors).clamp(min=0, max=1)
         else:
             boxes = boxes.sigmoid()
-        out = {"pred_logits": logits[-1], "pred_boxes": boxes[-1],
-               "pred_seg": self._seg_head(feats["P0"]) if self._seg_proxy else 0}
+        pred_seg = 0
+        if self._seg_proxy:
+            p0 = feats["P0"]
+            # the 1x1x1 head on csrc/seg_proxy.hip (GPU maps it takes); otherwise the stock convolution, as the reference
+            pred_seg = seg_proxy.seg_head(p0, self._seg_head) if seg_proxy.head_usable(p0, self._seg_head) else self._seg_head(p0)
+        out = {"pred_logits": logits[-1], "pred_boxes": boxes[-1], "pred_seg": pred_seg}
         if self._aux_loss:
             out["aux_outputs"] = [{"pred_logits": a, "pred_boxes": b} for a, b in zip(logits[:-1], boxes[:-1])]
         return out
