@@ -32,6 +32,7 @@ LIBS = {
     "libtransoar_optim.so": ["optim.hip"],
     "libtransoar_criterion.so": ["criterion.hip"],
     "libtransoar_segproxy.so": ["seg_proxy.hip"],
+    "libtransoar_boxtargets.so": ["box_targets.hip"],
 }
 
 

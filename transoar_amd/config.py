@@ -33,7 +33,7 @@ _NECK = dict(
 )
 _TOP = dict(
     lr=2e-4, lr_backbone=2e-5, weight_decay=1e-4, clip_max_norm=-1, lr_drop=2500, batch_size=2,
-    anchor_matching=True, set_cost_class=1, set_cost_bbox=0, set_cost_giou=0,
+    anchor_matching=True, set_cost_class=1, set_cost_bbox=0, set_cost_giou=0, bbox_padding=1,
     loss_coefs=dict(cls=2, bbox=5, giou=2, segce=2, segdice=2),
 )
 

@@ -41,6 +41,13 @@ class DenseTargets:
             num += int(t["labels"].shape[0])
         return DenseTargets(boxes, present, num)
 
+    @staticmethod
+    def from_labels(labels, num_organs, padding=1, min_extent=5):
+        """From a label volume (N, 1, D, H, W) or (N, D, H, W), on its device (box_targets.py: the reference's
+        segmentation2bbox); num_boxes and n_present are device scalars."""
+        from .box_targets import targets_from_labels
+        return targets_from_labels(labels, num_organs, padding, min_extent)
+
 
 class Matcher(nn.Module):
     def __init__(self, cost_class=1, cost_bbox=1, cost_giou=1, anchor_matching=True, num_organs=None):

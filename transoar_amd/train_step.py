@@ -11,7 +11,10 @@ weight decay 1e-4; optional gradient clipping, StepLR(lr_drop) stepped per epoch
     trainer.py:87-92): losses are returned as device tensors;
   * targets are densified once per step (DenseTargets) and the loss
     normalisers are all-reduced so N data-parallel replicas equal one process
-    on the concatenated batch.
+    on the concatenated batch;
+  * targets=None: the box targets are computed from the label volume (seg_targets)
+    on the device (box_targets.py; the reference's collator does it on the host,
+    data/dataloader.py:56) -- in the captured step as the first nodes of the graph.
 """
 import os
 
@@ -67,6 +70,7 @@ class TrainStep:
         self._static_counts = None
         self._static_counts_local = None
         self._static_seg = None
+        self._from_labels = False        # the captured step computes its box targets from the labels (capture(targets=None))
         self._expect_total = None
         self._want_graph = graph
         self.num_classes = config["num_classes"]
@@ -110,17 +114,16 @@ class TrainStep:
 
     def loss(self, data, targets, seg_targets=None, counts=None):
         """-> (weighted total, dict of unweighted losses); forward only.  counts: already
-        rank-summed loss normalisers (a 2-element device tensor), else they are reduced here."""
-        if not isinstance(targets, DenseTargets):
-            targets = DenseTargets.from_list(targets, self.num_classes, data.device)
+        rank-summed loss normalisers (a 2-element device tensor), else they are reduced here.
+        targets=None: the box targets come from the label volume seg_targets."""
+        targets = self._dense(data, targets, seg_targets)
         if counts is not None:
             targets = DenseTargets(targets.boxes, targets.present, counts[0], counts[1])
         pending = None
         if counts is None and self.reducer.active:
             # the rank-summed normalisers are only needed by the criterion: the sum is launched here and waited for after
             # the model's forward (no blocking collective opens a step)
-            counts = torch.stack((torch.as_tensor(float(targets.num_boxes), device=data.device),
-                                  targets.present.sum().float()))
+            counts = self._local_counts(targets)
             pending = self.reducer.reduce_counts_async(counts)
             targets = DenseTargets(targets.boxes, targets.present, counts[0], counts[1])
         enabled = self.amp_dtype is not None and self.amp_dtype != torch.float32
@@ -137,6 +140,23 @@ class TrainStep:
             losses = self.criterion(out, targets, seg_targets, self.model._anchors)
             total = self._weighted_total(losses)
         return total, losses
+
+    def _dense(self, data, targets, seg_targets):
+        """-> DenseTargets: as given, from the reference's list of dicts, or (targets=None) from the label volume."""
+        if isinstance(targets, DenseTargets):
+            return targets
+        if targets is None:
+            if not torch.is_tensor(seg_targets):
+                raise ValueError("TrainStep: targets=None computes the box targets from the label volume; pass it as seg_targets")
+            from .box_targets import targets_from_labels
+            return targets_from_labels(seg_targets.to(data.device), self.num_classes, int(self.config.get("bbox_padding", 1)))
+        return DenseTargets.from_list(targets, self.num_classes, data.device)
+
+    def _static_targets_from_labels(self):
+        """The box-target launches of the captured step: _static_seg -> _static_t and _static_counts, in place."""
+        from .box_targets import box_targets_into
+        box_targets_into(self._static_seg, self.num_classes, int(self.config.get("bbox_padding", 1)), 5, self._static_t.boxes,
+                         self._static_t.present, self._static_counts, self._box_ws)
 
     def _weighted_total(self, losses):
         """sum_k coef[k] * loss[k] as ONE stack and one dot product (eleven multiplies and ten adds, and as many nodes in the
@@ -169,22 +189,49 @@ class TrainStep:
     def capture(self, data, targets, seg_targets=None, warmup=3):
         """Capture fwd+loss+bwd for inputs of this shape.  Raises if anything in the step cannot be
         captured; the caller may then keep using the eager step.  With the segmentation proxy loss on, seg_targets
-        (the label volume) is required: it is copied into a static buffer that every replay refills."""
+        (the label volume) is required: it is copied into a static buffer that every replay refills.  targets=None: the box
+        targets are computed from that buffer by the first nodes of the graph (one GPU only), and replays take targets=None."""
         assert self._want_graph, "construct TrainStep(graph=True)"
-        if not isinstance(targets, DenseTargets):
+        from_labels = targets is None
+        if from_labels:
+            if not torch.is_tensor(seg_targets):
+                raise ValueError("TrainStep.capture: targets=None computes the box targets from the label volume; pass it as seg_targets")
+            if self.reducer.active:
+                raise RuntimeError("TrainStep.capture: targets=None is not supported with data parallelism yet; pass DenseTargets "
+                                   "(DenseTargets.from_labels) or use the eager step")
+            if not data.is_cuda:
+                raise RuntimeError("TrainStep.capture: a captured step needs CUDA tensors")
+        elif not isinstance(targets, DenseTargets):
             targets = DenseTargets.from_list(targets, self.num_classes, data.device)
         self.model.train()
         self._static_x = data.clone()
-        self._static_t = DenseTargets(targets.boxes.clone(), targets.present.clone(), targets.num_boxes)
         self._static_seg = None
-        if getattr(self.criterion, "_seg_proxy", False):
+        if from_labels or getattr(self.criterion, "_seg_proxy", False):
             if not torch.is_tensor(seg_targets):
                 raise RuntimeError("TrainStep.capture: the segmentation proxy loss is on; pass the label volume as seg_targets")
             self._static_seg = seg_targets.to(data.device).clone(memory_format=torch.contiguous_format)
+        self._from_labels = from_labels
+        if from_labels:
+            from . import box_targets
+            if not box_targets.usable(self._static_seg, self.num_classes):
+                raise RuntimeError("TrainStep.capture: the box-target kernels do not take labels of dtype %s and shape %s"
+                                   % (self._static_seg.dtype, tuple(self._static_seg.shape)))
+            n, k = data.shape[0], self.num_classes
+            self._box_ws = torch.empty(max(4, box_targets.workspace_bytes(n, self._static_seg[0].numel(), k)) // 4,
+                                       dtype=torch.int32, device=data.device)
+            self._static_counts = torch.empty(2, dtype=torch.float32, device=data.device)
+            self._static_t = DenseTargets(torch.empty(n, k, 6, dtype=torch.float32, device=data.device),
+                                          torch.empty(n, k, dtype=torch.bool, device=data.device),
+                                          self._static_counts[0], self._static_counts[1])
+        else:
+            self._static_t = DenseTargets(targets.boxes.clone(), targets.present.clone(), targets.num_boxes)
         # the loss normalisers (number of boxes, number of present classes) live in a static DEVICE buffer that
         # is refilled before every replay -- also on one GPU: a Python int would be baked into the captured
         # graph and mis-scale every batch whose box count differs from the captured one
-        self._static_counts = self._local_counts(self._static_t)
+        if from_labels:
+            self._static_targets_from_labels()
+        else:
+            self._static_counts = self._local_counts(self._static_t)
         # ... rank-summed.  With the exchange captured the sum is the graph's FIRST node (this rank's counts are written
         # to _static_counts_local before a replay, the graph copies them and all-reduces the copy): no host-launched
         # collective in front of a replay (round-4 VERDICT weak #16).  Otherwise an eager all-reduce before each replay.
@@ -204,6 +251,8 @@ class TrainStep:
         eager_total = None
         with torch.cuda.stream(side):
             for k in range(warmup):
+                if from_labels:
+                    self._static_targets_from_labels()
                 total = self._eager_fwd_bwd(self._static_x, self._static_t, self._static_seg)[0]
                 if k == 0:
                     eager_total = total          # the loss on the weights capture() was called with
@@ -247,6 +296,8 @@ class TrainStep:
                 if self._static_counts_local is not None:
                     self._static_counts.copy_(self._static_counts_local)
                     self.reducer.reduce_counts(self._static_counts)
+                if from_labels:                   # the labels are the step's only target input: boxes, present and counts from them
+                    self._static_targets_from_labels()
                 self._static_total, self._static_losses = self._eager_fwd_bwd(self._static_x, self._static_t, self._static_seg)
                 if self.capture_exchange:
                     self.reducer.exchange()       # buckets not launched by a hook yet, the joins, the widening copies
@@ -329,8 +380,13 @@ class TrainStep:
 
     @staticmethod
     def _local_counts(targets):
-        return torch.stack((torch.as_tensor(float(targets.num_boxes), device=targets.boxes.device),
-                            targets.present.sum().float()))
+        """[num_boxes, number of present (sample, class) slots] on the device; a tensor num_boxes is not read back."""
+        dev, num = targets.boxes.device, targets.num_boxes
+        if torch.is_tensor(num):
+            num = num.detach().to(device=dev, dtype=torch.float32).reshape(())
+        else:
+            num = torch.as_tensor(float(num), device=dev)
+        return torch.stack((num, targets.present.sum().float()))
 
     def _eager_fwd_bwd(self, data, targets, seg_targets=None):
         self.reducer.begin()
@@ -339,23 +395,30 @@ class TrainStep:
         return total.detach(), losses
 
     def _replay(self, data, targets, seg_targets=None):
+        if self._from_labels != (targets is None):
+            raise RuntimeError("TrainStep: this step was captured with %s; a replay takes the same form"
+                               % ("targets=None (the box targets are computed from seg_targets inside the graph)"
+                                  if self._from_labels else "explicit targets, targets=None needs a capture(data, None, labels)"))
         if self._static_seg is not None:
             # the labels are an input of the captured graph like the volume: copied in, never baked in
             if not torch.is_tensor(seg_targets) or seg_targets.shape != self._static_seg.shape \
                     or seg_targets.dtype != self._static_seg.dtype:
-                raise RuntimeError("TrainStep: the captured step (segmentation proxy loss on) needs seg_targets of shape %s and "
-                                   "dtype %s, got %s" % (tuple(self._static_seg.shape), self._static_seg.dtype,
+                raise RuntimeError("TrainStep: the captured step (%s) needs seg_targets of shape %s and "
+                                   "dtype %s, got %s" % ("segmentation proxy loss on" if getattr(self.criterion, "_seg_proxy", False)
+                                                         else "box targets from the labels", tuple(self._static_seg.shape), self._static_seg.dtype,
                                                          None if not torch.is_tensor(seg_targets) else
                                                          "%s %s" % (tuple(seg_targets.shape), seg_targets.dtype)))
             if seg_targets.data_ptr() != self._static_seg.data_ptr():
                 self._static_seg.copy_(seg_targets)
         if data.data_ptr() != self._static_x.data_ptr():
             self._static_x.copy_(data)
-        if targets is not self._static_t:
+        if targets is not None and targets is not self._static_t:
             self._static_t.boxes.copy_(targets.boxes)
             self._static_t.present.copy_(targets.present)
             self._static_t.num_boxes = targets.num_boxes
-        if self._static_counts_local is not None:
+        if self._from_labels:
+            pass                                 # boxes, present and counts are written by the graph's first nodes
+        elif self._static_counts_local is not None:
             self._static_counts_local.copy_(self._local_counts(self._static_t))      # summed over the ranks inside the graph
         else:
             self._static_counts.copy_(self._local_counts(self._static_t))
@@ -385,6 +448,7 @@ class TrainStep:
         self._static_counts = None
         self._static_counts_local = None
         self._static_seg = None
+        self._from_labels = False
         self.reducer.overlap = True
 
     def _clip(self):
@@ -394,7 +458,7 @@ class TrainStep:
 
     def __call__(self, data, targets, seg_targets=None):
         if self._graph is not None:
-            if not isinstance(targets, DenseTargets):
+            if targets is not None and not isinstance(targets, DenseTargets):
                 targets = DenseTargets.from_list(targets, self.num_classes, data.device)
             return self._replay(data, targets, seg_targets)
         self.model.train()
