@@ -83,11 +83,8 @@ def test_criterion_on_from_labels_equals_the_reference_lists(g13):
 
 
 def test_boxtargets_argument_errors():
-    lib = ctypes.CDLL(os.path.join(ROOT, "transoar_amd", "libtransoar_boxtargets.so"))
-    _p, _i, _l, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
+    from transoar_amd.box_targets import lib          # bound from include/transoar_boxtargets.h
     f, wb = lib.transoar_box_targets_forward, lib.transoar_box_targets_workspace_bytes
-    f.argtypes = [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]
-    wb.restype, wb.argtypes = _z, [_i, _l, _i]
     buf = (ctypes.c_char * 64)()
     p = (ctypes.addressof(buf) + 15) & ~15
     U8, I64 = 16, 19

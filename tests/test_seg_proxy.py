@@ -12,9 +12,6 @@ from oracle.torch_ref import msda3d_core_torch
 from tests._inputs import analytic_volume, fill_deterministic
 from tests._seg_inputs import LOSS_CASES, LOSS_GRAD_COEFS, P0_OUT, paint_labels, seg_model_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
 def relerr(a, b):
     a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
     return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-300)
@@ -78,21 +75,10 @@ def test_mirror_whole_model_against_g12b(g12, debug_core, tag, fg_bg):
         assert relerr(g, g12["b.%s.grad.%s" % (tag, n)]) <= 1e-7, n
 
 
-def _lib():
-    return ctypes.CDLL(os.path.join(ROOT, "transoar_amd", "libtransoar_segproxy.so"))
-
-
 def test_segproxy_argument_errors():
-    lib = _lib()
-    _p, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+    from transoar_amd.seg_proxy import lib          # bound from include/transoar_segproxy.h
     hf, hb = lib.transoar_seg_head_forward, lib.transoar_seg_head_backward
     lf, lb = lib.transoar_seg_loss_forward, lib.transoar_seg_loss_backward
-    hf.argtypes = [_p, _i, _i, _p, _p, _l, _l, _i, _i, _p, _p]
-    hb.argtypes = [_p, _i, _i, _p, _i, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p]
-    lf.argtypes = [_p, _i, _i, _p, _i, _l, _l, _i, _i, _f, _f, _p, _p, _p, _p]
-    lb.argtypes = [_p, _i, _i, _p, _i, _l, _l, _i, _i, _p, _p, _p, _p]
-    lib.transoar_seg_workspace_bytes.restype = ctypes.c_size_t
-    lib.transoar_seg_workspace_bytes.argtypes = [_i, _i]
     buf = (ctypes.c_char * 64)()
     p = ctypes.addressof(buf)
     NCDHW, NDHWC, F32, BF16, F16, U8, I64 = 0, 1, 0, 2, 3, 16, 19

@@ -11,27 +11,14 @@ TRANSOAR_BOX_TARGETS_HIP=0, and what the GPU tests compare the kernels with.
 One difference from the reference, in both paths: labels that are 0, negative or above num_classes are ignored (the reference
 would emit a class above num_classes, for which DenseTargets has no slot).
 """
-import ctypes
 import os
 
 import torch
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
 from .matcher import DenseTargets
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_boxtargets.so")
-if not os.path.exists(_LIB_PATH):
-    raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-lib = ctypes.CDLL(_LIB_PATH)
-_p, _i, _l, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_size_t
-lib.transoar_box_targets_workspace_bytes.restype = _z
-lib.transoar_box_targets_workspace_bytes.argtypes = [_i, _l, _i]
-lib.transoar_box_targets_forward.restype = _i
-lib.transoar_box_targets_forward.argtypes = [_p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]
-lib.transoar_boxtargets_abi_version.restype = _i
-if lib.transoar_boxtargets_abi_version() != 1:
-    raise _native.NativeLibraryError("%s: ABI version mismatch, rebuild" % _LIB_PATH)
-
+lib = _native.bind("boxtargets", abi=1)
 ENABLED = os.environ.get("TRANSOAR_BOX_TARGETS_HIP", "1") != "0"
 MAX_K = 64
 _LABEL_DT = {torch.uint8: 16, torch.int16: 17, torch.int32: 18, torch.int64: 19}
@@ -69,13 +56,9 @@ def box_targets_into(labels, num_classes, padding, min_extent, boxes, present, c
     need = workspace_bytes(n, sx * sy * sz, k)
     if workspace is None:
         workspace = torch.empty(max(need, 4) // 4, dtype=torch.int32, device=vol.device)
-    with torch.cuda.device(vol.device):
-        rc = lib.transoar_box_targets_forward(vol.data_ptr(), _LABEL_DT[vol.dtype], n, sx, sy, sz, k, int(padding), int(min_extent),
-                                              boxes.data_ptr(), present.data_ptr(), counts.data_ptr(), workspace.data_ptr(),
-                                              workspace.numel() * workspace.element_size(),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError("transoar_box_targets_forward failed with code %d" % rc)
+    _native.launch(lib.transoar_box_targets_forward, vol, vol.data_ptr(), _LABEL_DT[vol.dtype], n, sx, sy, sz, k, int(padding),
+                   int(min_extent), boxes.data_ptr(), present.data_ptr(), counts.data_ptr(), workspace.data_ptr(),
+                   workspace.numel() * workspace.element_size())
 
 
 def targets_from_labels(labels, num_classes, padding=1, min_extent=5, workspace=None):

@@ -9,66 +9,20 @@ gradient and its weight gradient run on the hand-written implicit-GEMM
 kernels, channels-last; otherwise (CPU tests, fp32/fp64 parity runs) it is
 the stock PyTorch convolution.
 """
-import ctypes
 import os
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
 from . import rows as _rows
 from . import conv_gemm as _cg
+from ._native import launch, ptr
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_PKG, "libtransoar_conv3d.so")
 ABI_VERSION = 5
-
-
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-    lib = ctypes.CDLL(_LIB_PATH)
-    i, p = ctypes.c_int, ctypes.c_void_p
-    lib.transoar_conv3d_k3_forward.restype = i
-    lib.transoar_conv3d_k3_forward.argtypes = [p, p, p, p] + [i] * 8 + [p]
-    lib.transoar_conv3d_k3_wgrad.restype = i
-    lib.transoar_conv3d_k3_wgrad.argtypes = [p, p, p] + [i] * 10 + [p]
-    lib.transoar_conv3d_k3_wgrad_lds.restype = i
-    lib.transoar_conv3d_k3_wgrad_lds.argtypes = [p, p, p, i] + [i] * 10 + [p]
-    lib.transoar_conv3d_k3_wgrad_tr.restype = i
-    lib.transoar_conv3d_k3_wgrad_tr.argtypes = [p, p, p, i] + [i] * 10 + [p]
-    lib.transoar_conv3d_c1_wgrad.restype = i
-    lib.transoar_conv3d_c1_wgrad.argtypes = [p, p, p, i] + [i] * 5 + [p]
-    lib.transoar_conv3d_c1_wgrad_tr.restype = i
-    lib.transoar_conv3d_c1_wgrad_tr.argtypes = [p, p, p, i] + [i] * 5 + [p]
-    lib.transoar_conv3d_k3_stat_rows.restype = i
-    lib.transoar_conv3d_k3_stat_rows.argtypes = [i] * 7
-    lib.transoar_conv3d_k3_forward_stats.restype = i
-    lib.transoar_conv3d_k3_forward_stats.argtypes = [p, p, p, p, p] + [i] * 6 + [p]
-    lib.transoar_conv3d_k3_forward_c1.restype = i
-    lib.transoar_conv3d_k3_forward_c1.argtypes = [p, p, p, p] + [i] * 5 + [p]
-    lib.transoar_conv3d_c1_forward.restype = i
-    lib.transoar_conv3d_c1_forward.argtypes = [p, p, p] + [i] * 5 + [p]
-    lib.transoar_layout_bf16.restype = i
-    lib.transoar_layout_bf16.argtypes = [p, p, i, ctypes.c_long, i, i, p]
-    lib.transoar_conv3d_abi_version.restype = i
-    if lib.transoar_conv3d_abi_version() != ABI_VERSION:
-        raise _native.NativeLibraryError("%s: ABI mismatch, rebuild" % _LIB_PATH)
-    return lib
-
-
-lib = _load()
+lib = _native.bind("conv3d", abi=ABI_VERSION)
 CL3D = torch.channels_last_3d
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed with code %d" % (what, rc))
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class _Relayout(torch.autograd.Function):
@@ -96,9 +50,7 @@ def _relayout_raw(t, to_channels_first):
     v = t.shape[2] * t.shape[3] * t.shape[4]
     out = torch.empty(t.shape, dtype=t.dtype, device=t.device,
                       memory_format=torch.contiguous_format if to_channels_first else CL3D)
-    with torch.cuda.device(t.device):
-        _check(lib.transoar_layout_bf16(t.data_ptr(), out.data_ptr(), n, v, c, 1 if to_channels_first else 0,
-                                        _stream()), "transoar_layout_bf16")
+    launch(lib.transoar_layout_bf16, t, t.data_ptr(), out.data_ptr(), n, v, c, 1 if to_channels_first else 0)
     return out
 
 
@@ -139,10 +91,8 @@ def conv3d_k3_forward(x, wk, bias, stride, dilated_input=False):
     else:
         od, oh, ow = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
     y = torch.empty((n, co, od, oh, ow), dtype=torch.bfloat16, device=x.device, memory_format=CL3D)
-    with torch.cuda.device(x.device):
-        _check(lib.transoar_conv3d_k3_forward(x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                              y.data_ptr(), n, d, h, w, ci, co, stride, 1 if dilated_input else 0,
-                                              _stream()), "transoar_conv3d_k3_forward")
+    launch(lib.transoar_conv3d_k3_forward, x, x.data_ptr(), wk.data_ptr(), ptr(bias),
+           y.data_ptr(), n, d, h, w, ci, co, stride, 1 if dilated_input else 0)
     return y
 
 
@@ -151,9 +101,7 @@ def conv3d_k3_forward_c1(x, wk, bias):
     n, _, d, h, w = x.shape
     cout = wk.shape[1]
     y = torch.empty((n, d, h, w, cout), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib.transoar_conv3d_k3_forward_c1(x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                 y.data_ptr(), n, d, h, w, cout, _stream()), "conv3d_k3_forward_c1")
+    launch(lib.transoar_conv3d_k3_forward_c1, x, x.data_ptr(), wk.data_ptr(), ptr(bias), y.data_ptr(), n, d, h, w, cout)
     return y.permute(0, 4, 1, 2, 3)
 
 
@@ -171,10 +119,8 @@ def conv3d_k3_forward_stats(x, wk, bias):
     else:
         y = torch.empty((n, co, d, h, w), dtype=torch.bfloat16, device=x.device, memory_format=CL3D)
     part = torch.empty((rows, 2, 32), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib.transoar_conv3d_k3_forward_stats(x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                    y.data_ptr(), part.data_ptr(), n, d, h, w, ci, co, _stream()),
-               "transoar_conv3d_k3_forward_stats")
+    launch(lib.transoar_conv3d_k3_forward_stats, x, x.data_ptr(), wk.data_ptr(), ptr(bias),
+           y.data_ptr(), part.data_ptr(), n, d, h, w, ci, co)
     return y, part
 
 
@@ -196,9 +142,8 @@ def conv3d_k3_wgrad(x, gy, stride):
     x_t3, gy_t = wgrad_operands(x, gy, stride)
     cin_p = (ci + 7) // 8 * 8
     dw = torch.zeros((27, co, cin_p), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib.transoar_conv3d_k3_wgrad(gy_t.data_ptr(), x_t3.data_ptr(), dw.data_ptr(), n, d, h, ow, ci,
-                                            od, oh, ow, co, stride, _stream()), "transoar_conv3d_k3_wgrad")
+    launch(lib.transoar_conv3d_k3_wgrad, x, gy_t.data_ptr(), x_t3.data_ptr(), dw.data_ptr(), n, d, h, ow, ci,
+           od, oh, ow, co, stride)
     return dw[:, :, :ci].view(3, 3, 3, co, ci).permute(3, 4, 0, 1, 2)
 
 
@@ -221,9 +166,8 @@ def conv3d_c1_wgrad(x, gy):
     tr = C1_WGRAD_TR and co % 8 == 0 and w % 64 == 0 and w <= 256          # coalesced loads + transposing LDS reads
     n_part = min(C1_WGRAD_TR_PARTIALS, n * d * h) if tr else min(C1_WGRAD_PARTIALS, max(1, (n * d * h + 3) // 4))
     partial = torch.empty((n_part, 32, 32), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        fn = lib.transoar_conv3d_c1_wgrad_tr if tr else lib.transoar_conv3d_c1_wgrad
-        _check(fn(x.data_ptr(), gy.data_ptr(), partial.data_ptr(), n_part, n, d, h, w, co, _stream()), "transoar_conv3d_c1_wgrad")
+    fn = lib.transoar_conv3d_c1_wgrad_tr if tr else lib.transoar_conv3d_c1_wgrad
+    launch(fn, x, x.data_ptr(), gy.data_ptr(), partial.data_ptr(), n_part, n, d, h, w, co)
     return _colsum(partial).view(32, 32)[:co, :27].reshape(co, 1, 3, 3, 3)
 
 
@@ -244,9 +188,7 @@ def conv3d_k3_wgrad_lds(x, gy):
             groups = LDS_WGRAD_TR_GROUPS if LDS_WGRAD_TR else LDS_WGRAD_GROUPS
             fn = lib.transoar_conv3d_k3_wgrad_tr if LDS_WGRAD_TR else lib.transoar_conv3d_k3_wgrad_lds
             partial = torch.empty((groups, 27, 32, 32), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                _check(fn(x.data_ptr(), gy.data_ptr(), partial.data_ptr(), groups, n, d, h, w, ci, co, ci0, ci_n, co0, co_n, _stream()),
-                       "transoar_conv3d_k3_wgrad_lds")
+            launch(fn, x, x.data_ptr(), gy.data_ptr(), partial.data_ptr(), groups, n, d, h, w, ci, co, ci0, ci_n, co0, co_n)
             dw[co0:co0 + co_n, ci0:ci0 + ci_n] = _colsum(partial).view(27, 32, 32)[:, :co_n, :ci_n].permute(1, 2, 0)
     return dw.view(co, ci, 3, 3, 3)
 

@@ -4,49 +4,16 @@ layers (encoder_blocks.py:28-51, attn_fpn.py:65-73,126), forward, data gradient 
 mirrored tap list; stride 2: the eight parity classes of the dx voxels in one launch -- up to 32 input channels the
 halo-tile kernel that writes dx as whole lines) and weight gradient -- and the
 weight gradient of a token projection as the one-tap case.  No fallback: the library must be built."""
-import ctypes
 import os
 
 import torch
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
+from ._native import launch, ptr
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_PKG, "libtransoar_convgemm.so")
 ABI_VERSION = 3
 CL3D = torch.channels_last_3d
-
-
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-    lib = ctypes.CDLL(_LIB_PATH)
-    i, p, u = ctypes.c_int, ctypes.c_void_p, ctypes.c_uint
-    lib.transoar_conv3d_igemm.restype = i
-    lib.transoar_conv3d_igemm.argtypes = [p] * 5 + [i] * 17 + [u] * 3 + [i, i, p]
-    lib.transoar_conv3d_finish.restype = i
-    lib.transoar_conv3d_finish.argtypes = [p, p, p, ctypes.c_long, i, i, p]
-    lib.transoar_conv3d_wgrad.restype = i
-    lib.transoar_conv3d_wgrad.argtypes = [p, p, p, p] + [i] * 10 + [u] * 3 + [i, i, p]
-    lib.transoar_linear_wgrad_bias.restype = i
-    lib.transoar_linear_wgrad_bias.argtypes = [p] * 6 + [i] * 4 + [p]
-    lib.transoar_conv3d_wgrad_ring.restype = i
-    lib.transoar_conv3d_wgrad_ring.argtypes = [p, p, p, p] + [i] * 11 + [p]
-    lib.transoar_conv3d_wgrad_part_floats.restype = ctypes.c_long
-    lib.transoar_conv3d_wgrad_part_floats.argtypes = [i, i, i, i]
-    lib.transoar_conv3d_dgrad_s2_halo.restype = i
-    lib.transoar_conv3d_dgrad_s2_halo.argtypes = [p, p, p] + [i] * 9 + [p]
-    lib.transoar_conv3d_pack.restype = i
-    lib.transoar_conv3d_pack.argtypes = [p, p, p, i, i, p]
-    lib.transoar_conv3d_pack_many.restype = i
-    lib.transoar_conv3d_pack_many.argtypes = [p, i, ctypes.c_long, p]
-    lib.transoar_convgemm_abi_version.restype = i
-    if lib.transoar_convgemm_abi_version() != ABI_VERSION:
-        raise _native.NativeLibraryError("%s: ABI mismatch, rebuild" % _LIB_PATH)
-    return lib
-
-
-lib = _load()
+lib = _native.bind("convgemm", abi=ABI_VERSION)
 
 
 def _taps(entries):
@@ -66,15 +33,6 @@ TAPS_ONE = _taps([(0, 1)])
 SPLIT_BELOW_TILES = 384
 DGRAD_S2_HALO = os.environ.get("TRANSOAR_DGRAD_S2_HALO", "1") != "0"
 WGRAD_BLOCKS = 512          # workgroups of a weight-gradient launch: one resident set (2 per CU); 2x for very long or very wide problems
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed with code %d" % (what, rc))
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def pack_fwd(weight):
@@ -98,8 +56,7 @@ def pack_both(weight):
         return pack_fwd(weight), pack_dgrad(weight)
     wk = torch.empty((27, co, ci), dtype=torch.bfloat16, device=weight.device)
     wkt = torch.empty((27, ci, co), dtype=torch.bfloat16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        _check(lib.transoar_conv3d_pack(weight.data_ptr(), wk.data_ptr(), wkt.data_ptr(), co, ci, _stream()), "transoar_conv3d_pack")
+    launch(lib.transoar_conv3d_pack, weight, weight.data_ptr(), wk.data_ptr(), wkt.data_ptr(), co, ci)
     return wk, wkt
 
 
@@ -131,9 +88,7 @@ class PackPlan:
         return all(m.weight.data_ptr() == p for m, p in zip(self.modules, self.ptrs))
 
     def run(self):
-        with torch.cuda.device(self.table.device):
-            _check(lib.transoar_conv3d_pack_many(self.table.data_ptr(), len(self.modules), self.total_tiles, _stream()),
-                   "transoar_conv3d_pack_many")
+        launch(lib.transoar_conv3d_pack_many, self.table, self.table.data_ptr(), len(self.modules), self.total_tiles)
         for m, packs in zip(self.modules, self.buffers):
             m._packs, m._packs_version = packs, m.weight._version
 
@@ -151,20 +106,15 @@ def _tiles(rows, cout):
 
 def _igemm(x, wk, bias, out, src_dims, cin, cout, m_dims, src_stride, out_dims, out_stride, parity, taps, n, split, classes=0):
     """One launch of transoar_conv3d_igemm (+ the summing / cast pass when split > 1); `out` is the whole output map."""
-    b = bias.data_ptr() if bias is not None else None
-    with torch.cuda.device(x.device):
-        if split > 1:
-            rows_out = n * out_dims[0] * out_dims[1] * out_dims[2]
-            part = torch.empty((split, rows_out, cout), dtype=torch.float32, device=x.device)      # written completely
-            _check(lib.transoar_conv3d_igemm(x.data_ptr(), wk.data_ptr(), None, None, part.data_ptr(), n, *src_dims, cin, cout,
-                                             *m_dims, src_stride, *out_dims, out_stride, *parity, *taps, split, classes, _stream()),
-                   "transoar_conv3d_igemm")
-            _check(lib.transoar_conv3d_finish(part.data_ptr(), b, out.data_ptr(), rows_out, cout, split, _stream()),
-                   "transoar_conv3d_finish")
-        else:
-            _check(lib.transoar_conv3d_igemm(x.data_ptr(), wk.data_ptr(), b, out.data_ptr(), None, n, *src_dims, cin, cout,
-                                             *m_dims, src_stride, *out_dims, out_stride, *parity, *taps, 1, classes, _stream()),
-                   "transoar_conv3d_igemm")
+    if split > 1:
+        rows_out = n * out_dims[0] * out_dims[1] * out_dims[2]
+        part = torch.empty((split, rows_out, cout), dtype=torch.float32, device=x.device)      # written completely
+        launch(lib.transoar_conv3d_igemm, x, x.data_ptr(), wk.data_ptr(), None, None, part.data_ptr(), n, *src_dims, cin, cout,
+               *m_dims, src_stride, *out_dims, out_stride, *parity, *taps, split, classes)
+        launch(lib.transoar_conv3d_finish, x, part.data_ptr(), ptr(bias), out.data_ptr(), rows_out, cout, split)
+    else:
+        launch(lib.transoar_conv3d_igemm, x, x.data_ptr(), wk.data_ptr(), ptr(bias), out.data_ptr(), None, n, *src_dims, cin, cout,
+               *m_dims, src_stride, *out_dims, out_stride, *parity, *taps, 1, classes)
 
 
 MAX_ROWS = 1 << 21          # rows (voxels of the row space) per launch: the kernels decompose a row index with float reciprocals
@@ -220,9 +170,7 @@ def conv_dgrad(gy, wkt, stride, in_dims, split=None):
         return gx
     if split is None and DGRAD_S2_HALO and ci <= 32 and co in (16, 32, 48):
         # few input channels, full-resolution dx: one workgroup computes all eight parity classes of a dx tile (HBM bound)
-        with torch.cuda.device(gy.device):
-            _check(lib.transoar_conv3d_dgrad_s2_halo(gy.data_ptr(), wkt.data_ptr(), gx.data_ptr(), n, od, oh, ow, d, h, w, ci, co, _stream()),
-                   "transoar_conv3d_dgrad_s2_halo")
+        launch(lib.transoar_conv3d_dgrad_s2_halo, gy, gy.data_ptr(), wkt.data_ptr(), gx.data_ptr(), n, od, oh, ow, d, h, w, ci, co)
         return gx
     # stride 2: the eight parity classes (pd, ph, pw) of the dx voxels in one launch: 1, 2, 4 or 8 taps each
     if split is None:
@@ -243,9 +191,8 @@ def _wgrad(x2, gy2, geom, taps, taps_out, out_shape):
     chunks = max(1, min(budget // tiles, rows // 1024 if rows >= 1024 else 1))      # >= 16 K steps of 64 rows per block
     part = torch.empty(lib.transoar_conv3d_wgrad_part_floats(ci, co, chunks, taps_out), dtype=torch.float32, device=x2.device)
     dw = torch.empty(out_shape, dtype=torch.float32, device=x2.device)
-    with torch.cuda.device(x2.device):
-        _check(lib.transoar_conv3d_wgrad(gy2.data_ptr(), x2.data_ptr(), part.data_ptr(), dw.data_ptr(), n, sd, sh, sw, ci, co, md, mh, mw,
-                                         stride, *taps, chunks, taps_out, _stream()), "transoar_conv3d_wgrad")
+    launch(lib.transoar_conv3d_wgrad, x2, gy2.data_ptr(), x2.data_ptr(), part.data_ptr(), dw.data_ptr(), n, sd, sh, sw, ci, co,
+           md, mh, mw, stride, *taps, chunks, taps_out)
     return dw
 
 
@@ -266,9 +213,8 @@ def conv_wgrad_ring(x, gy, stride, chunks=None):
     chunks = chunks or WGRAD_RING_CHUNKS
     part = torch.empty(lib.transoar_conv3d_wgrad_part_floats(ci, co, chunks, 27), dtype=torch.float32, device=x.device)
     dw = torch.empty((co, ci, 3, 3, 3), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib.transoar_conv3d_wgrad_ring(gy.data_ptr(), x.data_ptr(), part.data_ptr(), dw.data_ptr(), n, d, h, w, ci, co, od, oh, ow,
-                                              stride, chunks, _stream()), "transoar_conv3d_wgrad_ring")
+    launch(lib.transoar_conv3d_wgrad_ring, x, gy.data_ptr(), x.data_ptr(), part.data_ptr(), dw.data_ptr(), n, d, h, w, ci, co,
+           od, oh, ow, stride, chunks)
     return dw
 
 
@@ -312,9 +258,8 @@ def linear_wgrad_bias(x, gy):
     bias_part = torch.empty(chunks * nn_, dtype=torch.float32, device=x.device)
     dw = torch.empty((nn_, k), dtype=torch.float32, device=x.device)
     db = torch.empty(nn_, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib.transoar_linear_wgrad_bias(gy.data_ptr(), x.data_ptr(), part.data_ptr(), dw.data_ptr(), bias_part.data_ptr(), db.data_ptr(),
-                                              t, k, nn_, chunks, _stream()), "transoar_linear_wgrad_bias")
+    launch(lib.transoar_linear_wgrad_bias, x, gy.data_ptr(), x.data_ptr(), part.data_ptr(), dw.data_ptr(), bias_part.data_ptr(),
+           db.data_ptr(), t, k, nn_, chunks)
     return dw, db
 
 

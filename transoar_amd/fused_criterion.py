@@ -13,34 +13,14 @@ import os
 
 import torch
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
 from . import seg_proxy
+from ._native import launch, ptr
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_criterion.so")
-if not os.path.exists(_LIB_PATH):
-    raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-lib = ctypes.CDLL(_LIB_PATH)
-_p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-lib.transoar_set_criterion_forward.restype = _i
-lib.transoar_set_criterion_forward.argtypes = [_p, _i, _i, _p, _i, _p, _p, _p, _p, _f, _p, _f, _f, _f, _i, _i, _i, _p, _p, _p, _p, _p, _p]
-lib.transoar_set_criterion_backward.restype = _i
-lib.transoar_set_criterion_backward.argtypes = [_p, _i, _p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p]
-lib.transoar_criterion_abi_version.restype = _i
-if lib.transoar_criterion_abi_version() != 1:
-    raise _native.NativeLibraryError("%s: ABI version mismatch, rebuild" % _LIB_PATH)
-
+lib = _native.bind("criterion", abi=1)
 ENABLED = os.environ.get("TRANSOAR_FUSED_CRITERION", "1") != "0"
 MAX_LAYERS, MAX_R = 8, 64
 _DT = {torch.float32: 0, torch.bfloat16: 2}
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed with code %d" % (what, rc))
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class LossDict(dict):
@@ -100,13 +80,11 @@ class _SetCriterion(torch.autograd.Function):
         d_giou = torch.empty(n, q, 6, dtype=torch.float32, device=dev)
         d_cls = torch.empty(n, q, dtype=torch.float32, device=dev)
         hit = torch.empty(layers, n, q, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _check(lib.transoar_set_criterion_forward(
-                ctypes.cast(ptrs, ctypes.c_void_p), layers, _DT[logits.dtype], boxes.data_ptr(), _DT[boxes.dtype], anchors.data_ptr(),
-                tgt_boxes.data_ptr(), present8.data_ptr(), None if nb_dev is None else nb_dev.data_ptr(), nb_host,
-                None if np_dev is None else np_dev.data_ptr(), float(costs[0]), float(costs[1]), float(costs[2]), n, num_classes, r,
-                losses.data_ptr(), d_l1.data_ptr(), d_giou.data_ptr(), d_cls.data_ptr(), hit.data_ptr(), _stream()),
-                "transoar_set_criterion_forward")
+        launch(lib.transoar_set_criterion_forward, logits,
+               ctypes.cast(ptrs, ctypes.c_void_p), layers, _DT[logits.dtype], boxes.data_ptr(), _DT[boxes.dtype], anchors.data_ptr(),
+               tgt_boxes.data_ptr(), present8.data_ptr(), ptr(nb_dev), nb_host,
+               ptr(np_dev), float(costs[0]), float(costs[1]), float(costs[2]), n, num_classes, r,
+               losses.data_ptr(), d_l1.data_ptr(), d_giou.data_ptr(), d_cls.data_ptr(), hit.data_ptr())
         ctx.save_for_backward(d_l1, d_giou, d_cls, hit)
         ctx.dims = (layers, n, num_classes, r, logits.dtype, boxes.dtype, tuple(logits.shape))
         return losses
@@ -118,10 +96,8 @@ class _SetCriterion(torch.autograd.Function):
         g = g.contiguous().float()
         grad_boxes = torch.empty(n, o * r, 6, dtype=bdt, device=g.device)
         grad_logits = torch.empty(lshape, dtype=ldt, device=g.device)
-        with torch.cuda.device(g.device):
-            _check(lib.transoar_set_criterion_backward(g.data_ptr(), layers, d_l1.data_ptr(), d_giou.data_ptr(), d_cls.data_ptr(),
-                                                       hit.data_ptr(), n, o, r, grad_boxes.data_ptr(), _DT[bdt], grad_logits.data_ptr(),
-                                                       _DT[ldt], _stream()), "transoar_set_criterion_backward")
+        launch(lib.transoar_set_criterion_backward, g, g.data_ptr(), layers, d_l1.data_ptr(), d_giou.data_ptr(), d_cls.data_ptr(),
+               hit.data_ptr(), n, o, r, grad_boxes.data_ptr(), _DT[bdt], grad_logits.data_ptr(), _DT[ldt])
         return grad_logits, grad_boxes, None, None, None, None, None, None, None, None
 
 

@@ -1,15 +1,13 @@
 """ctypes binding of the gfx950 token GEMM (include/transoar_gemm.h): ``linear_nt(x, w, bias, relu)`` =
 ``relu?(x @ w.T + bias)`` for bf16/f16 operands with fp32 accumulation.  No fallback: raises if the library is
 missing."""
-import ctypes
 import os
 
 import torch
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
+from ._native import launch, ptr
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_PKG, "libtransoar_gemm.so")
 ABI_VERSION = 4
 STREAM_SQUARE = os.environ.get("TRANSOAR_GEMM_STREAM_SQUARE", "0") == "1"
 STREAM_N384 = os.environ.get("TRANSOAR_GEMM_N384", "0") == "1"
@@ -17,36 +15,7 @@ STREAM = os.environ.get("TRANSOAR_GEMM_STREAM", "1") != "0"      # the K = 384 /
 _DT = {torch.float32: 0, torch.bfloat16: 2, torch.float16: 3}
 
 
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-    lib = ctypes.CDLL(_LIB_PATH)
-    i, p = ctypes.c_int, ctypes.c_void_p
-    lib.transoar_gemm_nt.restype = i
-    lib.transoar_gemm_nt.argtypes = [p, p, p, p] + [i] * 9 + [p]
-    lib.transoar_gemm_nt_gelu.restype = i
-    lib.transoar_gemm_nt_gelu.argtypes = [p, p, p, p, p] + [i] * 7 + [p]
-    lib.transoar_gemm_k384.restype = i
-    lib.transoar_gemm_k384.argtypes = [p, p, p, p, i, i, i, p]
-    lib.transoar_gemm_k384_drop.restype = i
-    lib.transoar_gemm_k384_drop.argtypes = [p, p, p, p, i, i, i, p, ctypes.c_float, ctypes.c_float, p]
-    lib.transoar_gemm_k384_gate.restype = i
-    lib.transoar_gemm_k384_gate.argtypes = [p, p, p, p, i, i, ctypes.c_float, p]
-    lib.transoar_gemm_n384.restype = i
-    lib.transoar_gemm_n384.argtypes = [p, p, p, p, i, i, p]
-    lib.transoar_gemm_wgrad384_chunks.restype = i
-    lib.transoar_gemm_wgrad384_chunks.argtypes = [i, i]
-    lib.transoar_gemm_wgrad384.restype = i
-    lib.transoar_gemm_wgrad384.argtypes = [p, p, p, p, i, i, i, i, p]
-    lib.transoar_gemm_wgrad384_bias.restype = i
-    lib.transoar_gemm_wgrad384_bias.argtypes = [p, p, p, p, i, i, i, i, p, p, i, p]
-    lib.transoar_gemm_abi_version.restype = i
-    if lib.transoar_gemm_abi_version() != ABI_VERSION:
-        raise _native.NativeLibraryError("%s: ABI mismatch, rebuild" % _LIB_PATH)
-    return lib
-
-
-lib = _load()
+lib = _native.bind("gemm", abi=ABI_VERSION)
 
 
 def usable(x, w):
@@ -96,23 +65,13 @@ def linear_nt(x, w, bias=None, relu=False, out_dtype=None):
     kind = stream_kind(x, w, out_dtype)
     if kind == "n384" and relu:
         kind = None
-    if kind is not None:
-        with torch.cuda.device(x.device):
-            bp = None if bias is None else bias.data_ptr()
-            if kind == "k384":
-                rc = lib.transoar_gemm_k384(x.data_ptr(), w.data_ptr(), bp, out.data_ptr(), m, n, 1 if relu else 0,
-                                            torch.cuda.current_stream().cuda_stream)
-            else:
-                rc = lib.transoar_gemm_n384(x.data_ptr(), w.data_ptr(), bp, out.data_ptr(), m, k, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_gemm_%s failed with code %d" % (kind, rc))
-        return out
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_gemm_nt(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(),
-                                  m, n, k, x.stride(0), w.stride(0), n, _DT[x.dtype], _DT[out_dtype], 1 if relu else 0,
-                                  torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_gemm_nt failed with code %d" % rc)
+    if kind == "k384":
+        launch(lib.transoar_gemm_k384, x, x.data_ptr(), w.data_ptr(), ptr(bias), out.data_ptr(), m, n, 1 if relu else 0)
+    elif kind == "n384":
+        launch(lib.transoar_gemm_n384, x, x.data_ptr(), w.data_ptr(), ptr(bias), out.data_ptr(), m, k)
+    else:
+        launch(lib.transoar_gemm_nt, x, x.data_ptr(), w.data_ptr(), ptr(bias), out.data_ptr(),
+               m, n, k, x.stride(0), w.stride(0), n, _DT[x.dtype], _DT[out_dtype], 1 if relu else 0)
     return out
 
 
@@ -132,11 +91,8 @@ def linear_gelu(x, w, bias=None):
     a = torch.empty_like(h)
     if bias is not None:
         bias = bias.float().contiguous()
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_gemm_nt_gelu(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), a.data_ptr(), h.data_ptr(),
-                                       m, n, k, x.stride(0), w.stride(0), n, 1, torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_gemm_nt_gelu failed with code %d" % rc)
+    launch(lib.transoar_gemm_nt_gelu, x, x.data_ptr(), w.data_ptr(), ptr(bias), a.data_ptr(), h.data_ptr(),
+           m, n, k, x.stride(0), w.stride(0), n, 1)
     return h, a
 
 
@@ -148,11 +104,8 @@ def linear_gelu_grad(gy, wt, h):
     m, k = gy.shape
     n = wt.shape[0]
     out = torch.empty((m, n), dtype=torch.bfloat16, device=gy.device)
-    with torch.cuda.device(gy.device):
-        rc = lib.transoar_gemm_nt_gelu(gy.data_ptr(), wt.data_ptr(), None, out.data_ptr(), h.data_ptr(), m, n, k, gy.stride(0),
-                                       wt.stride(0), n, 2, torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_gemm_nt_gelu failed with code %d" % rc)
+    launch(lib.transoar_gemm_nt_gelu, gy, gy.data_ptr(), wt.data_ptr(), None, out.data_ptr(), h.data_ptr(), m, n, k,
+           gy.stride(0), wt.stride(0), n, 2)
     return out
 
 
@@ -166,12 +119,8 @@ def linear_relu_dropout(x, w, bias, seed, keep_prob):
     out = torch.empty((m, n), dtype=torch.bfloat16, device=x.device)
     if bias is not None:
         bias = bias.float().contiguous()
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_gemm_k384_drop(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), out.data_ptr(), m, n, 1,
-                                         None if seed is None else seed.data_ptr(), float(keep_prob), 1.0 / float(keep_prob),
-                                         torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_gemm_k384_drop failed with code %d" % rc)
+    launch(lib.transoar_gemm_k384_drop, x, x.data_ptr(), w.data_ptr(), ptr(bias), out.data_ptr(), m, n, 1,
+           ptr(seed), float(keep_prob), 1.0 / float(keep_prob))
     return out
 
 
@@ -212,12 +161,8 @@ def wgrad384(gy, x, with_bias=False):
     out = torch.empty((n, k), dtype=torch.float32, device=gy.device)
     bias_part = torch.empty((chunks, n), dtype=torch.float32, device=gy.device) if with_bias else None
     db = torch.empty((n,), dtype=torch.float32, device=gy.device) if with_bias else None
-    with torch.cuda.device(gy.device):
-        rc = lib.transoar_gemm_wgrad384_bias(a.data_ptr(), b.data_ptr(), part.data_ptr(), out.data_ptr(), t, na, tr, chunks,
-                                             bias_part.data_ptr() if with_bias else None, db.data_ptr() if with_bias else None,
-                                             side if with_bias else 0, torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_gemm_wgrad384 failed with code %d" % rc)
+    launch(lib.transoar_gemm_wgrad384_bias, gy, a.data_ptr(), b.data_ptr(), part.data_ptr(), out.data_ptr(), t, na, tr, chunks,
+           ptr(bias_part), ptr(db), side if with_bias else 0)
     return (out, db) if with_bias else out
 
 
@@ -230,9 +175,5 @@ def linear_gate(x, w, gate, scale):
     if (m + 32) * n * 2 >= 0xffffffff:
         raise RuntimeError("linear_gate: the gate is addressed with 32-bit byte offsets; chunk over the rows")
     out = torch.empty((m, n), dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_gemm_k384_gate(x.data_ptr(), w.data_ptr(), gate.data_ptr(), out.data_ptr(), m, n, float(scale),
-                                         torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_gemm_k384_gate failed with code %d" % rc)
+    launch(lib.transoar_gemm_k384_gate, x, x.data_ptr(), w.data_ptr(), gate.data_ptr(), out.data_ptr(), m, n, float(scale))
     return out

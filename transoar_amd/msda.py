@@ -115,13 +115,10 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     sampling_loc, attn_weight = _coerce_loc(value, sampling_loc, attn_weight)
     out = torch.empty((N, Lq, M * C), dtype=value.dtype, device=value.device)
     _keep, host_ptr = _shapes_on_host(spatial_shapes)
-    with torch.cuda.device(value.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = _native.lib.transoar_msda3d_forward(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-            sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(),
-            N, S, M, C, L, Lq, P, _DT[value.dtype], _DT[sampling_loc.dtype], host_ptr, flags, stream)
-    _native.check(rc, "transoar_msda3d_forward")
+    _native.launch(_native.lib.transoar_msda3d_forward, value,
+                   value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                   sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(),
+                   N, S, M, C, L, Lq, P, _DT[value.dtype], _DT[sampling_loc.dtype], host_ptr, flags)
     return out
 
 
@@ -145,15 +142,10 @@ def ms_deform_attn_forward_fused(value, spatial_shapes, proj, reference_points, 
     out = torch.empty((N, S, M * C), dtype=value.dtype, device=value.device)
     _keep, host_ptr = _shapes_on_host(spatial_shapes)
     _require(host_ptr is not None, "the fused gather needs the level shapes on the host (locality_hint)")
-    with torch.cuda.device(value.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = _native.lib.transoar_msda3d_forward_fused(
-            value.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), reference_points.size(0) * S,
-            out.data_ptr(), N, S, M, C, L, P, _DT[value.dtype], host_ptr, stream)
-    if rc == -2 and not strict:           # TRANSOAR_ERR_DIM: not a form the fused kernel covers
-        return None
-    _native.check(rc, "transoar_msda3d_forward_fused")
-    return out
+    rc = _native.launch(_native.lib.transoar_msda3d_forward_fused, value,
+                        value.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), reference_points.size(0) * S,
+                        out.data_ptr(), N, S, M, C, L, P, _DT[value.dtype], host_ptr, ok=() if strict else (-2,))
+    return None if rc else out          # -2, TRANSOAR_ERR_DIM: not a form the fused kernel covers
 
 
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
@@ -176,20 +168,18 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
     _keep, host_ptr = _shapes_on_host(spatial_shapes)
     torch_det = torch.are_deterministic_algorithms_enabled()
 
-    def run(call_flags):
+    def run(call_flags, ok=()):
         ws_bytes = _native.lib.transoar_msda3d_backward_workspace_bytes(*dims, call_flags)
         workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=value.device)
-        with torch.cuda.device(value.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            return _native.lib.transoar_msda3d_backward(
-                value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
-                workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags, stream)
+        return _native.launch(_native.lib.transoar_msda3d_backward, value,
+                              value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                              sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
+                              grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
+                              workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags, ok=ok)
 
-    if deterministic or torch_det or (flags & DETERMINISTIC):
-        rc = run(flags | DETERMINISTIC)
-        if rc == ERR_MODE and not (deterministic or (flags & DETERMINISTIC)):
+    strict = deterministic or bool(flags & DETERMINISTIC)          # the switch itself: an uncovered form raises
+    if strict or torch_det:
+        if run(flags | DETERMINISTIC, ok=() if strict else (ERR_MODE,)) == ERR_MODE:
             if not torch.is_deterministic_algorithms_warn_only_enabled():
                 raise RuntimeError("ms_deform_attn_backward does not have a deterministic implementation for this form (16-bit "
                                    "storage, 64 channels, 4 points, <= 4 levels with queries = the pyramid's voxels are covered), "
@@ -197,10 +187,9 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
             import warnings
             warnings.warn("ms_deform_attn_backward: no deterministic implementation for this form; running the default "
                           "(atomic-order dependent) accumulation")
-            rc = run(flags)
+            run(flags)
     else:
-        rc = run(flags)
-    _native.check(rc, "transoar_msda3d_backward")
+        run(flags)
     return [grad_value, grad_loc.to(loc_in_dtype), grad_attn.to(attn_in_dtype)]
 
 
@@ -223,12 +212,8 @@ def ms_deform_attn_backward_proj(value, spatial_shapes, level_start_index, sampl
     _keep, host_ptr = _shapes_on_host(spatial_shapes)
     ws_bytes = _native.lib.transoar_msda3d_backward_workspace_bytes(*dims, call_flags)
     workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=value.device)
-    with torch.cuda.device(value.device):
-        rc = _native.lib.transoar_msda3d_backward_proj(
-            value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-            attn_weight.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(), grad_proj.data_ptr(),
-            workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags, torch.cuda.current_stream().cuda_stream)
-    if rc == ERR_MODE:
-        return None
-    _native.check(rc, "transoar_msda3d_backward_proj")
-    return [grad_value, grad_proj]
+    rc = _native.launch(_native.lib.transoar_msda3d_backward_proj, value,
+                        value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+                        attn_weight.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(), grad_proj.data_ptr(),
+                        workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags, ok=(ERR_MODE,))
+    return None if rc else [grad_value, grad_proj]

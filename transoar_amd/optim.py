@@ -5,22 +5,11 @@ and learning rates on the device as with capturable=True), state_dict / load_sta
 torch's own -- only step() is replaced.  torch's fused implementation runs the flagship's 335 tensors as eight
 multi_tensor_apply launches, 0.60 ms per step; this one moves the same 28 bytes per parameter in 0.3 ms.
 Reference: scripts/train.py:52-63 (AdamW, two learning rates, weight decay 1e-4)."""
-import ctypes
-import os
-
 import torch
 
-from . import _native  # noqa: F401
+from . import _native
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_optim.so")
-if not os.path.exists(_LIB_PATH):
-    raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-lib = ctypes.CDLL(_LIB_PATH)
-lib.transoar_adamw_step.restype = ctypes.c_int
-lib.transoar_adamw_step.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_double] * 2 + [ctypes.c_float] * 2 + [ctypes.c_void_p]
-lib.transoar_optim_abi_version.restype = ctypes.c_int
-if lib.transoar_optim_abi_version() != 1:
-    raise _native.NativeLibraryError("%s: ABI version mismatch, rebuild" % _LIB_PATH)
+lib = _native.bind("optim", abi=1)
 CHUNK = 16384
 _MAX_TABLES = 32
 
@@ -152,11 +141,8 @@ class FlatAdamW(torch.optim.AdamW):
             return loss
         torch._foreach_add_(steps, 1.0)
         tab, ids, offs, n_chunks = self._table(rows, device)[:4]
-        with torch.cuda.device(device):
-            rc = lib.transoar_adamw_step(tab.data_ptr(), ids.data_ptr(), offs.data_ptr(), n_chunks, betas[0], betas[1], eps, wd,
-                                         torch.cuda.current_stream().cuda_stream)
-        if rc:
-            raise RuntimeError("transoar_adamw_step failed with code %d" % rc)
+        _native.launch(lib.transoar_adamw_step, tab, tab.data_ptr(), ids.data_ptr(), offs.data_ptr(), n_chunks,
+                       betas[0], betas[1], eps, wd)
         # the kernel wrote through raw pointers: tell autograd (and the bf16 mirrors' staleness check) that the weights changed
         torch.autograd.graph.increment_version([r[0] for r in rows])
         return loss

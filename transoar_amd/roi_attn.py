@@ -9,43 +9,18 @@ in the folded per-organ form of focused_decoder._roi_attention_folded: per (batc
 Forward is one kernel (QK^T -> mask -> online softmax -> PV; plus a small combine pass when the keys are split across
 workgroups); the backward recomputes P from the saved log-sum-exp in two kernels.  No fallback: the library must be built.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
+from ._native import launch
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_attn.so")
 ABI_VERSION = 2
 CHANNELS = 384
 MAX_ROWS = 512
-
-
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-    lib = ctypes.CDLL(_LIB_PATH)
-    i, p, l, z = ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_size_t
-    lib.transoar_roi_attn_workspace_bytes.restype = z
-    lib.transoar_roi_attn_workspace_bytes.argtypes = [i, i, i]
-    lib.transoar_roi_attn_forward.restype = i
-    lib.transoar_roi_attn_forward.argtypes = [p, p, p, p, p, p, p, p, z, i, i, i, l, i, i, p]
-    lib.transoar_roi_attn_backward.restype = i
-    lib.transoar_roi_attn_backward.argtypes = [p, p, p, p, p, p, p, p, p, p, p, z, i, i, i, l, i, i, p]
-    lib.transoar_attn_abi_version.restype = i
-    if lib.transoar_attn_abi_version() != ABI_VERSION:
-        raise _native.NativeLibraryError("%s: ABI mismatch, rebuild" % _LIB_PATH)
-    return lib
-
-
-lib = _load()
+lib = _native.bind("attn", abi=ABI_VERSION)
 ENABLED = os.environ.get("TRANSOAR_ROI_FUSED", "1") != "0"
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed with code %d" % (what, rc))
 
 
 def key_mask(pad):
@@ -93,10 +68,6 @@ def pick_split(groups, rows):
     return max(1, min(8, 256 // max(blocks, 1)))
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 class RoiAttention(torch.autograd.Function):
     """ctx = softmax(mask(qf k^T)) v per (batch, organ).  The gradient of the keys is handed to `v_tok` together with the
     values' (callers pass keys = values + input-independent positions, focused_decoder._FoldedCore's convention); `k_tok`
@@ -114,10 +85,8 @@ class RoiAttention(torch.autograd.Function):
         lse = torch.empty((g, r), dtype=torch.float32, device=qf.device)
         ws_bytes = lib.transoar_roi_attn_workspace_bytes(g, r, split)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qf.device)
-        with torch.cuda.device(qf.device):
-            _check(lib.transoar_roi_attn_forward(qf.data_ptr(), k_tok.data_ptr(), v_tok.data_ptr(), bits.data_ptr(), n_tiles.data_ptr(),
-                                                 out.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws_bytes, g, o, r, n_keys, c, split,
-                                                 _stream()), "transoar_roi_attn_forward")
+        launch(lib.transoar_roi_attn_forward, qf, qf.data_ptr(), k_tok.data_ptr(), v_tok.data_ptr(), bits.data_ptr(),
+               n_tiles.data_ptr(), out.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws_bytes, g, o, r, n_keys, c, split)
         ctx.save_for_backward(qf, k_tok, v_tok, out, lse, bits, n_tiles)
         ctx.split = split
         return out
@@ -133,11 +102,9 @@ class RoiAttention(torch.autograd.Function):
         dtok = torch.empty_like(v_tok)
         ws_bytes = lib.transoar_roi_attn_workspace_bytes(g, r, ctx.split)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qf.device)
-        with torch.cuda.device(qf.device):
-            _check(lib.transoar_roi_attn_backward(qf.data_ptr(), k_tok.data_ptr(), v_tok.data_ptr(), out.data_ptr(), dctx.data_ptr(),
-                                                  lse.data_ptr(), bits.data_ptr(), n_tiles.data_ptr(), dq.data_ptr(), dtok.data_ptr(),
-                                                  ws.data_ptr(), ws_bytes, g, o, r, n_keys, c, ctx.split, _stream()),
-                   "transoar_roi_attn_backward")
+        launch(lib.transoar_roi_attn_backward, qf, qf.data_ptr(), k_tok.data_ptr(), v_tok.data_ptr(), out.data_ptr(),
+               dctx.data_ptr(), lse.data_ptr(), bits.data_ptr(), n_tiles.data_ptr(), dq.data_ptr(), dtok.data_ptr(),
+               ws.data_ptr(), ws_bytes, g, o, r, n_keys, c, ctx.split)
         return dq, None, dtok, None, None
 
 

@@ -1,28 +1,9 @@
 """ctypes shim of the row gather / inverse-gather kernels (include/transoar_rows.h)."""
-import ctypes
-import os
-
 import torch
 
-from . import _native  # noqa: F401
+from . import _native
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_rows.so")
-if not os.path.exists(_LIB_PATH):
-    raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-lib = ctypes.CDLL(_LIB_PATH)
-_i, _p, _l = ctypes.c_int, ctypes.c_void_p, ctypes.c_long
-lib.transoar_rows_gather.restype = _i
-lib.transoar_rows_gather.argtypes = [_p, _p, _p, _i, _l, _l, _i, _p]
-lib.transoar_rows_gather_axpy.restype = _i
-lib.transoar_rows_gather_axpy.argtypes = [_p, _p, _p, _p, _p, _i, _l, _l, _i, _p]
-lib.transoar_rows_pull_sum.restype = _i
-lib.transoar_rows_pull_sum.argtypes = [_p, _p, _p, _p, _i, _l, _l, _i, _i, _p]
-lib.transoar_rows_colsum.restype = _i
-lib.transoar_rows_colsum.argtypes = [_p, _p, _p, _l, _i, _p]
-lib.transoar_rows_colsum_workspace_floats.restype = _i
-lib.transoar_rows_colsum_workspace_floats.argtypes = [_i]
-lib.transoar_rows_colsum_small.restype = _i
-lib.transoar_rows_colsum_small.argtypes = [_p, _p, _l, _i, _i, _p]
+lib = _native.bind("rows")          # the one library without a version function
 
 
 def colsum_usable(x):
@@ -35,11 +16,7 @@ def colsum(x):
     rows, cols = x.shape
     out = torch.empty(cols, dtype=torch.float32, device=x.device)
     work = torch.empty(lib.transoar_rows_colsum_workspace_floats(cols), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_rows_colsum(x.data_ptr(), out.data_ptr(), work.data_ptr(), rows, cols,
-                                      torch.cuda.current_stream().cuda_stream)
-    if rc:
-        raise RuntimeError("transoar_rows_colsum failed with code %d" % rc)
+    _native.launch(lib.transoar_rows_colsum, x, x.data_ptr(), out.data_ptr(), work.data_ptr(), rows, cols)
     return out
 
 
@@ -52,11 +29,8 @@ def colsum_small(x):
     """x (rows, cols) bf16 / fp32 contiguous, a short matrix -> (cols,) fp32 column sums in one launch."""
     rows, cols = x.shape
     out = torch.empty(cols, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_rows_colsum_small(x.data_ptr(), out.data_ptr(), rows, cols, int(x.dtype == torch.bfloat16),
-                                            torch.cuda.current_stream().cuda_stream)
-    if rc:
-        raise RuntimeError("transoar_rows_colsum_small failed with code %d" % rc)
+    _native.launch(lib.transoar_rows_colsum_small, x, x.data_ptr(), out.data_ptr(), rows, cols,
+                   int(x.dtype == torch.bfloat16))
     return out
 
 
@@ -92,11 +66,8 @@ def gather(x, index):
         s = x.stride(0) // c            # rows between batch elements
     k = index.numel()
     out = torch.empty((b, k, c), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_rows_gather(x.data_ptr(), index.data_ptr(), out.data_ptr(), b, s, k,
-                                      c * x.element_size(), torch.cuda.current_stream().cuda_stream)
-    if rc:
-        raise RuntimeError("transoar_rows_gather failed with code %d" % rc)
+    _native.launch(lib.transoar_rows_gather, x, x.data_ptr(), index.data_ptr(), out.data_ptr(), b, s, k,
+                   c * x.element_size())
     return out
 
 
@@ -114,12 +85,8 @@ def gather_axpy(x, index, scale=None, resid=None):
     if resid is not None and tuple(resid.shape) != (b, k, c):
         raise RuntimeError("gather_axpy: residual must be (B, K, C)")
     out = torch.empty((b, k, c), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_rows_gather_axpy(x.data_ptr(), index.data_ptr(), None if scale is None else scale.data_ptr(),
-                                           None if resid is None else resid.data_ptr(), out.data_ptr(), b, s, k,
-                                           c * x.element_size(), torch.cuda.current_stream().cuda_stream)
-    if rc:
-        raise RuntimeError("transoar_rows_gather_axpy failed with code %d" % rc)
+    _native.launch(lib.transoar_rows_gather_axpy, x, x.data_ptr(), index.data_ptr(), _native.ptr(scale),
+                   _native.ptr(resid), out.data_ptr(), b, s, k, c * x.element_size())
     return out
 
 
@@ -127,10 +94,6 @@ def pull_sum(g, inv_ptr, inv_idx, n_tokens):
     """g (B,K,C) contiguous -> (B,S,C): sum of the rows listed per token"""
     b, k, c = g.shape
     out = torch.empty((b, n_tokens, c), dtype=g.dtype, device=g.device)
-    with torch.cuda.device(g.device):
-        rc = lib.transoar_rows_pull_sum(g.data_ptr(), inv_ptr.data_ptr(), inv_idx.data_ptr(), out.data_ptr(), b,
-                                        n_tokens, k, c * g.element_size(), 1 if g.dtype == torch.bfloat16 else 0,
-                                        torch.cuda.current_stream().cuda_stream)
-    if rc:
-        raise RuntimeError("transoar_rows_pull_sum failed with code %d" % rc)
+    _native.launch(lib.transoar_rows_pull_sum, g, g.data_ptr(), inv_ptr.data_ptr(), inv_idx.data_ptr(), out.data_ptr(), b,
+                   n_tokens, k, c * g.element_size(), 1 if g.dtype == torch.bfloat16 else 0)
     return out

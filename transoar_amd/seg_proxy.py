@@ -8,46 +8,19 @@ expect it there), and the losses are the criterion's.  The torch code they repla
 TransoarCriterion.loss_segmentation's softmax / one-hot / tp-fp-fn tensors at full resolution) stays the path for CPU
 tensors, shapes the kernels do not take, and TRANSOAR_SEG_PROXY_HIP=0; it is what the GPU tests compare these kernels with.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _native  # noqa: F401  (torch's HIP runtime first)
+from . import _native
+from ._native import launch, ptr
 
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libtransoar_segproxy.so")
-if not os.path.exists(_LIB_PATH):
-    raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-lib = ctypes.CDLL(_LIB_PATH)
-_p, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
-lib.transoar_seg_workspace_bytes.restype = ctypes.c_size_t
-lib.transoar_seg_workspace_bytes.argtypes = [_i, _i]
-lib.transoar_seg_head_forward.restype = _i
-lib.transoar_seg_head_forward.argtypes = [_p, _i, _i, _p, _p, _l, _l, _i, _i, _p, _p]
-lib.transoar_seg_head_backward.restype = _i
-lib.transoar_seg_head_backward.argtypes = [_p, _i, _i, _p, _i, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p]
-lib.transoar_seg_loss_forward.restype = _i
-lib.transoar_seg_loss_forward.argtypes = [_p, _i, _i, _p, _i, _l, _l, _i, _i, _f, _f, _p, _p, _p, _p]
-lib.transoar_seg_loss_backward.restype = _i
-lib.transoar_seg_loss_backward.argtypes = [_p, _i, _i, _p, _i, _l, _l, _i, _i, _p, _p, _p, _p]
-lib.transoar_segproxy_abi_version.restype = _i
-if lib.transoar_segproxy_abi_version() != 1:
-    raise _native.NativeLibraryError("%s: ABI version mismatch, rebuild" % _LIB_PATH)
-
+lib = _native.bind("segproxy", abi=1)
 ENABLED = os.environ.get("TRANSOAR_SEG_PROXY_HIP", "1") != "0"
 MAX_C, MAX_K = 64, 32
 NCDHW, NDHWC = 0, 1
 _DT = {torch.float32: 0, torch.bfloat16: 2}
 _LABEL_DT = {torch.uint8: 16, torch.int16: 17, torch.int32: 18, torch.int64: 19}
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed with code %d" % (what, rc))
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _layout(t):
@@ -82,9 +55,8 @@ class _SegHead(torch.autograd.Function):
         w32 = weight.detach().reshape(k, c).float().contiguous()
         b32 = bias.detach().float().contiguous()
         y = torch.empty((n, k, d, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last_3d)
-        with torch.cuda.device(x.device):
-            _check(lib.transoar_seg_head_forward(x.data_ptr(), xl, _DT[x.dtype], w32.data_ptr(), b32.data_ptr(), n, d * h * w, c, k,
-                                                 y.data_ptr(), _stream()), "transoar_seg_head_forward")
+        launch(lib.transoar_seg_head_forward, x, x.data_ptr(), xl, _DT[x.dtype], w32.data_ptr(), b32.data_ptr(), n, d * h * w, c, k,
+               y.data_ptr())
         ctx.save_for_backward(x, w32)
         ctx.meta = (xl, weight.shape, weight.dtype, bias.dtype)
         return y
@@ -100,10 +72,8 @@ class _SegHead(torch.autograd.Function):
         dw = torch.empty(k, c, dtype=torch.float32, device=x.device)
         db = torch.empty(k, dtype=torch.float32, device=x.device)
         ws = _workspace(c, k, x.device)
-        with torch.cuda.device(x.device):
-            _check(lib.transoar_seg_head_backward(x.data_ptr(), xl, _DT[x.dtype], dy.data_ptr(), dyl, w32.data_ptr(), n, d * h * w, c, k,
-                                                  None if dx is None else dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
-                                                  _stream()), "transoar_seg_head_backward")
+        launch(lib.transoar_seg_head_backward, x, x.data_ptr(), xl, _DT[x.dtype], dy.data_ptr(), dyl, w32.data_ptr(), n, d * h * w, c, k,
+               ptr(dx), dw.data_ptr(), db.data_ptr(), ws.data_ptr())
         return dx, dw.view(wshape).to(wdt), db.to(bdt)
 
 
@@ -134,10 +104,9 @@ class _SegLosses(torch.autograd.Function):
         losses = torch.empty(2, dtype=torch.float32, device=logits.device)
         stats = torch.empty(2 * k, dtype=torch.float32, device=logits.device)
         ws = _workspace(0, k, logits.device)
-        with torch.cuda.device(logits.device):
-            _check(lib.transoar_seg_loss_forward(logits.data_ptr(), ll, _DT[logits.dtype], labels.data_ptr(), _LABEL_DT[labels.dtype],
-                                                 n, s, k, int(bool(fg_bg)), float(smooth_nom), float(smooth_denom), losses.data_ptr(),
-                                                 stats.data_ptr(), ws.data_ptr(), _stream()), "transoar_seg_loss_forward")
+        launch(lib.transoar_seg_loss_forward, logits, logits.data_ptr(), ll, _DT[logits.dtype], labels.data_ptr(),
+               _LABEL_DT[labels.dtype], n, s, k, int(bool(fg_bg)), float(smooth_nom), float(smooth_denom), losses.data_ptr(),
+               stats.data_ptr(), ws.data_ptr())
         ctx.save_for_backward(logits, labels, stats)
         ctx.meta = (ll, bool(fg_bg))
         ctx.mark_non_differentiable(stats)
@@ -150,10 +119,8 @@ class _SegLosses(torch.autograd.Function):
         n, k = logits.shape[0], logits.shape[1]
         g = g.contiguous().float()          # the two upstream gradients stay on the device (a graph tensor in the captured step)
         grad = torch.empty_like(logits)     # same layout as the logits
-        with torch.cuda.device(logits.device):
-            _check(lib.transoar_seg_loss_backward(logits.data_ptr(), ll, _DT[logits.dtype], labels.data_ptr(), _LABEL_DT[labels.dtype],
-                                                  n, logits[0, 0].numel(), k, int(fg_bg), stats.data_ptr(), g.data_ptr(),
-                                                  grad.data_ptr(), _stream()), "transoar_seg_loss_backward")
+        launch(lib.transoar_seg_loss_backward, logits, logits.data_ptr(), ll, _DT[logits.dtype], labels.data_ptr(),
+               _LABEL_DT[labels.dtype], n, logits[0, 0].numel(), k, int(fg_bg), stats.data_ptr(), g.data_ptr(), grad.data_ptr())
         return grad, None, None, None, None
 
 

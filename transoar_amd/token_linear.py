@@ -167,11 +167,7 @@ class _LinearReluDropout(torch.autograd.Function):
         xb, wb, y = ctx.saved_tensors
         gy2 = gy.to(torch.bfloat16).reshape(-1, gy.shape[-1]).contiguous()
         gh = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            rc = tokens.lib.transoar_relu_dropout_backward(gy2.data_ptr(), y.data_ptr(), ctx.scale, gh.data_ptr(), y.numel(),
-                                                           torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_relu_dropout_backward failed with code %d" % rc)
+        tokens.launch(tokens.lib.transoar_relu_dropout_backward, y, gy2.data_ptr(), y.data_ptr(), ctx.scale, gh.data_ptr(), y.numel())
         gx = gw = gb = None
         with torch.autocast("cuda", enabled=False):
             if ctx.needs_input_grad[0]:

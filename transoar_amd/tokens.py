@@ -7,53 +7,15 @@
 next layer ``round(y + (pos_sine + level_embed[level]))`` -- one pass over the
 tokens instead of add, layer_norm, two casts, the positional add and its cast.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _native  # noqa: F401
+from . import _native
 from . import rows as _rows
+from ._native import launch, ptr
 
-_PKG = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_PKG, "libtransoar_tokens.so")
-
-
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise _native.NativeLibraryError("%s is not built (python transoar_amd/_build.py)" % _LIB_PATH)
-    lib = ctypes.CDLL(_LIB_PATH)
-    i, p, lg, f = ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.c_float
-    lib.transoar_add_layernorm_forward.restype = i
-    lib.transoar_add_layernorm_forward.argtypes = [p, i, p, p, p, f, p, p, p, i, lg, p, p, p, p, lg, i, p, f, p, f, p]
-    lib.transoar_add_layernorm_backward.restype = i
-    lib.transoar_add_layernorm_backward.argtypes = [p, p, p, p, i, p, p, p, p, i, lg, p, p, p, lg, i, p, f, p, f, p]
-    lib.transoar_relu_dropout_forward.restype = i
-    lib.transoar_relu_dropout_forward.argtypes = [p, p, f, p, f, p, lg, p]
-    lib.transoar_relu_dropout_backward.restype = i
-    lib.transoar_relu_dropout_backward.argtypes = [p, p, f, p, lg, p]
-    lib.transoar_add_layernorm_partial_rows.restype = i
-    lib.transoar_sampling_head_forward.restype = i
-    lib.transoar_sampling_head_forward.argtypes = [p, p, lg, p, p, p, lg, i, i, i, p]
-    lib.transoar_sampling_head_backward.restype = i
-    lib.transoar_sampling_head_backward.argtypes = [p, p, p, p, p, lg, i, i, i, p]
-    lib.transoar_pos_query_forward.restype = i
-    lib.transoar_pos_query_forward.argtypes = [p, p, p, p, i, lg, p, lg, i, p]
-    lib.transoar_pos_query_backward.restype = i
-    lib.transoar_pos_query_backward.argtypes = [p, p, i, lg, p, lg, i, p]
-    lib.transoar_pos_query_partial_rows.restype = i
-    lib.transoar_ln_rows_forward.restype = i
-    lib.transoar_ln_rows_forward.argtypes = [p, i, p, p, ctypes.c_float, p, p, p, lg, i, p]
-    lib.transoar_ln_rows_backward.restype = i
-    lib.transoar_ln_rows_backward.argtypes = [p, p, i, p, p, p, p, p, p, lg, i, p]
-    lib.transoar_ln_rows_partial_rows.restype = i
-    lib.transoar_tokens_abi_version.restype = i
-    if lib.transoar_tokens_abi_version() != 7:
-        raise _native.NativeLibraryError("%s: ABI mismatch, rebuild" % _LIB_PATH)
-    return lib
-
-
-lib = _load()
+lib = _native.bind("tokens", abi=7)
 PARTIAL_ROWS = lib.transoar_add_layernorm_partial_rows()
 POS_QUERY_PARTIAL_ROWS = lib.transoar_pos_query_partial_rows()
 
@@ -62,10 +24,6 @@ def usable(x, r, cols):
     return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()
             and (r is None or (r.dtype == torch.bfloat16 and r.is_contiguous() and r.shape == x.shape))
             and cols % 128 == 0 and cols // 128 in (1, 2, 3, 4, 6, 8))
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _keep_args(keep, scale):
@@ -94,14 +52,10 @@ class _AddLayerNorm(torch.autograd.Function):
         n_lvl = level_embed.shape[0] if with_q else 0
         s_tokens = pos_sine.shape[0] if with_q else rows
         le32 = level_embed.float().contiguous() if with_q else None
-        with torch.cuda.device(x.device):
-            rc = lib.transoar_add_layernorm_forward(
-                x.data_ptr(), int(x.dtype == torch.bfloat16), _ptr(r), w32.data_ptr(), b32.data_ptr(), float(eps),
-                _ptr(pos_sine), _ptr(le32), _ptr(level_start), n_lvl, s_tokens, y32.data_ptr(), y16.data_ptr(),
-                _ptr(q16), stats.data_ptr(), rows, cols, *_keep_args(keep, keep_scale),
-                torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_add_layernorm_forward failed with code %d" % rc)
+        launch(lib.transoar_add_layernorm_forward, x,
+               x.data_ptr(), int(x.dtype == torch.bfloat16), ptr(r), w32.data_ptr(), b32.data_ptr(), float(eps),
+               ptr(pos_sine), ptr(le32), ptr(level_start), n_lvl, s_tokens, y32.data_ptr(), y16.data_ptr(),
+               ptr(q16), stats.data_ptr(), rows, cols, *_keep_args(keep, keep_scale))
         ctx.save_for_backward(x, r, w32, stats, level_start, keep)
         ctx.keep_scale = float(keep_scale)
         ctx.n_lvl, ctx.s_tokens, ctx.with_q = n_lvl, s_tokens, with_q
@@ -124,14 +78,10 @@ class _AddLayerNorm(torch.autograd.Function):
             gr = torch.empty_like(r)
         n_lvl = ctx.n_lvl if gq16 is not None else 0
         partials = torch.empty((PARTIAL_ROWS, 2 + n_lvl, cols), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.transoar_add_layernorm_backward(
-                _ptr(g32), _ptr(g16), _ptr(gq16), x.data_ptr(), int(x_bf16), _ptr(r), w32.data_ptr(),
-                stats.data_ptr(), _ptr(level_start), n_lvl, ctx.s_tokens, gx.data_ptr(), _ptr(gr),
-                partials.data_ptr(), rows, cols, *_keep_args(keep, ctx.keep_scale),
-                torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_add_layernorm_backward failed with code %d" % rc)
+        launch(lib.transoar_add_layernorm_backward, x,
+               ptr(g32), ptr(g16), ptr(gq16), x.data_ptr(), int(x_bf16), ptr(r), w32.data_ptr(),
+               stats.data_ptr(), ptr(level_start), n_lvl, ctx.s_tokens, gx.data_ptr(), ptr(gr),
+               partials.data_ptr(), rows, cols, *_keep_args(keep, ctx.keep_scale))
         sums = _rows.colsum_any(partials.view(PARTIAL_ROWS, -1)).view(2 + n_lvl, cols)     # one launch (rows.colsum_small)
         g_le = None
         if ctx.with_q and ctx.needs_input_grad[6]:
@@ -196,12 +146,8 @@ class _PosQuery(torch.autograd.Function):
         rows = x16.numel() // cols
         le32 = level_embed.float().contiguous()
         q16 = torch.empty_like(x16)
-        with torch.cuda.device(x16.device):
-            rc = lib.transoar_pos_query_forward(x16.data_ptr(), pos_sine.data_ptr(), le32.data_ptr(),
-                                                level_start.data_ptr(), le32.shape[0], pos_sine.shape[0],
-                                                q16.data_ptr(), rows, cols, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_pos_query_forward failed with code %d" % rc)
+        launch(lib.transoar_pos_query_forward, x16, x16.data_ptr(), pos_sine.data_ptr(), le32.data_ptr(),
+               level_start.data_ptr(), le32.shape[0], pos_sine.shape[0], q16.data_ptr(), rows, cols)
         ctx.save_for_backward(level_start)
         ctx.dims = (rows, cols, le32.shape[0], pos_sine.shape[0], level_embed.dtype)
         return q16
@@ -214,12 +160,8 @@ class _PosQuery(torch.autograd.Function):
         g_le = None
         if ctx.needs_input_grad[2]:
             partials = torch.empty((POS_QUERY_PARTIAL_ROWS, n_lvl, cols), dtype=torch.float32, device=gq.device)
-            with torch.cuda.device(gq.device):
-                rc = lib.transoar_pos_query_backward(gq.data_ptr(), level_start.data_ptr(), n_lvl, s_tokens,
-                                                     partials.data_ptr(), rows, cols,
-                                                     torch.cuda.current_stream().cuda_stream)
-            if rc != 0:
-                raise RuntimeError("transoar_pos_query_backward failed with code %d" % rc)
+            launch(lib.transoar_pos_query_backward, gq, gq.data_ptr(), level_start.data_ptr(), n_lvl, s_tokens,
+                   partials.data_ptr(), rows, cols)
             g_le = _rows.colsum_any(partials.view(POS_QUERY_PARTIAL_ROWS, -1)).view(n_lvl, cols).to(le_dtype)
         return gq, None, g_le, None           # d q / d x = 1: the query's gradient IS the tokens' gradient
 
@@ -234,11 +176,7 @@ class _ReluDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, keep, scale):
         y = torch.empty_like(h)
-        with torch.cuda.device(h.device):
-            rc = lib.transoar_relu_dropout_forward(h.data_ptr(), *_keep_args(keep, scale), y.data_ptr(), h.numel(),
-                                                   torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_relu_dropout_forward failed with code %d" % rc)
+        launch(lib.transoar_relu_dropout_forward, h, h.data_ptr(), *_keep_args(keep, scale), y.data_ptr(), h.numel())
         ctx.save_for_backward(y)
         ctx.scale = float(scale)
         return y
@@ -248,11 +186,7 @@ class _ReluDropout(torch.autograd.Function):
         y, = ctx.saved_tensors
         gy = gy.contiguous()
         gh = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            rc = lib.transoar_relu_dropout_backward(gy.data_ptr(), y.data_ptr(), ctx.scale, gh.data_ptr(), y.numel(),
-                                                    torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_relu_dropout_backward failed with code %d" % rc)
+        launch(lib.transoar_relu_dropout_backward, y, gy.data_ptr(), y.data_ptr(), ctx.scale, gh.data_ptr(), y.numel())
         return gh, None, None
 
 
@@ -272,13 +206,8 @@ class _SamplingHead(torch.autograd.Function):
         n, lq, _ = proj.shape
         loc = torch.empty((n, lq, m, lv, pt, 3), dtype=torch.float32, device=proj.device)
         attn = torch.empty((n, lq, m, lv, pt), dtype=torch.float32, device=proj.device)
-        with torch.cuda.device(proj.device):
-            rc = lib.transoar_sampling_head_forward(proj.data_ptr(), reference_points.data_ptr(),
-                                                    reference_points.shape[0] * lq, shapes.data_ptr(),
-                                                    loc.data_ptr(), attn.data_ptr(), n * lq, m, lv, pt,
-                                                    torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_sampling_head_forward failed with code %d" % rc)
+        launch(lib.transoar_sampling_head_forward, proj, proj.data_ptr(), reference_points.data_ptr(),
+               reference_points.shape[0] * lq, shapes.data_ptr(), loc.data_ptr(), attn.data_ptr(), n * lq, m, lv, pt)
         ctx.save_for_backward(attn, shapes)
         ctx.dims = (m, lv, pt, proj.shape)
         return loc, attn
@@ -289,12 +218,8 @@ class _SamplingHead(torch.autograd.Function):
         m, lv, pt, shape = ctx.dims
         g_loc, g_attn = g_loc.contiguous(), g_attn.contiguous()
         g_proj = torch.empty(shape, dtype=torch.bfloat16, device=attn.device)
-        with torch.cuda.device(attn.device):
-            rc = lib.transoar_sampling_head_backward(g_loc.data_ptr(), g_attn.data_ptr(), attn.data_ptr(), shapes.data_ptr(),
-                                                     g_proj.data_ptr(), shape[0] * shape[1], m, lv, pt,
-                                                     torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("transoar_sampling_head_backward failed with code %d" % rc)
+        launch(lib.transoar_sampling_head_backward, attn, g_loc.data_ptr(), g_attn.data_ptr(), attn.data_ptr(),
+               shapes.data_ptr(), g_proj.data_ptr(), shape[0] * shape[1], m, lv, pt)
         return g_proj, None, None, None, None, None
 
 
@@ -303,23 +228,15 @@ def sampling_head_raw(proj, reference_points, shapes, m, lv, pt):
     n, lq, _ = proj.shape
     loc = torch.empty((n, lq, m, lv, pt, 3), dtype=torch.float32, device=proj.device)
     attn = torch.empty((n, lq, m, lv, pt), dtype=torch.float32, device=proj.device)
-    with torch.cuda.device(proj.device):
-        rc = lib.transoar_sampling_head_forward(proj.data_ptr(), reference_points.data_ptr(), reference_points.shape[0] * lq,
-                                                shapes.data_ptr(), loc.data_ptr(), attn.data_ptr(), n * lq, m, lv, pt,
-                                                torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_sampling_head_forward failed with code %d" % rc)
+    launch(lib.transoar_sampling_head_forward, proj, proj.data_ptr(), reference_points.data_ptr(),
+           reference_points.shape[0] * lq, shapes.data_ptr(), loc.data_ptr(), attn.data_ptr(), n * lq, m, lv, pt)
     return loc, attn
 
 
 def sampling_head_backward_raw(g_loc, g_attn, attn, shapes, m, lv, pt, proj_shape):
     g_proj = torch.empty(proj_shape, dtype=torch.bfloat16, device=attn.device)
-    with torch.cuda.device(attn.device):
-        rc = lib.transoar_sampling_head_backward(g_loc.data_ptr(), g_attn.data_ptr(), attn.data_ptr(), shapes.data_ptr(),
-                                                 g_proj.data_ptr(), proj_shape[0] * proj_shape[1], m, lv, pt,
-                                                 torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_sampling_head_backward failed with code %d" % rc)
+    launch(lib.transoar_sampling_head_backward, attn, g_loc.data_ptr(), g_attn.data_ptr(), attn.data_ptr(),
+           shapes.data_ptr(), g_proj.data_ptr(), proj_shape[0] * proj_shape[1], m, lv, pt)
     return g_proj
 
 
@@ -345,12 +262,8 @@ def _ln_rows_forward(x, weight, bias, eps):
     mean = torch.empty(n_rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(n_rows, dtype=torch.float32, device=x.device)
     w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_ln_rows_forward(x.data_ptr(), int(x.dtype == torch.bfloat16), w32.data_ptr(), b32.data_ptr(), float(eps),
-                                          y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), n_rows, cols,
-                                          torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_ln_rows_forward failed with code %d" % rc)
+    launch(lib.transoar_ln_rows_forward, x, x.data_ptr(), int(x.dtype == torch.bfloat16), w32.data_ptr(), b32.data_ptr(),
+           float(eps), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), n_rows, cols)
     return y, w32, mean, rstd
 
 
@@ -362,12 +275,8 @@ def _ln_rows_backward(g, x, w32, mean, rstd, g_add=None):
         g_add = g_add.to(x.dtype).contiguous()
     dx = torch.empty_like(x)
     partials = torch.empty((lib.transoar_ln_rows_partial_rows(), 2 * cols), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.transoar_ln_rows_backward(g.data_ptr(), x.data_ptr(), int(x.dtype == torch.bfloat16), w32.data_ptr(), mean.data_ptr(),
-                                           rstd.data_ptr(), _ptr(g_add), dx.data_ptr(), partials.data_ptr(), n_rows, cols,
-                                           torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("transoar_ln_rows_backward failed with code %d" % rc)
+    launch(lib.transoar_ln_rows_backward, x, g.data_ptr(), x.data_ptr(), int(x.dtype == torch.bfloat16), w32.data_ptr(),
+           mean.data_ptr(), rstd.data_ptr(), ptr(g_add), dx.data_ptr(), partials.data_ptr(), n_rows, cols)
     from . import rows
     sums = rows.colsum_any(partials)
     return dx, sums[:cols], sums[cols:]

@@ -12,17 +12,12 @@ import torch
 import torch.nn.functional as F
 
 from . import roi_attn
+from ._native import launch, ptr
 
-lib = roi_attn.lib
+lib = roi_attn.lib            # both attention families live in libtransoar_attn.so
 HEAD_DIMS = (16, 32)          # the shipped configurations have 16 (48 / 96 / 192 / 384 channels, 3 / 6 / 12 / 24 heads)
 MAX_TOKENS = 128
 ENABLED = os.environ.get("TRANSOAR_WIN_ATTN", "1") != "0"
-
-_i, _p, _f = roi_attn.ctypes.c_int, roi_attn.ctypes.c_void_p, roi_attn.ctypes.c_float
-lib.transoar_win_attn_forward.restype = _i
-lib.transoar_win_attn_forward.argtypes = [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]
-lib.transoar_win_attn_backward.restype = _i
-lib.transoar_win_attn_backward.argtypes = [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]
 
 
 def mask_bits(mask):
@@ -51,10 +46,8 @@ class _WindowAttention(torch.autograd.Function):
         bias_pad = F.pad(bias.detach().float(), (0, MAX_TOKENS - n)).contiguous()
         out = torch.empty((b, n_win, n, c3 // 3), dtype=torch.bfloat16, device=qkv.device)
         lse2 = torch.empty((windows, heads, n), dtype=torch.float32, device=qkv.device)
-        with torch.cuda.device(qkv.device):
-            roi_attn._check(lib.transoar_win_attn_forward(qkv.data_ptr(), bias_pad.data_ptr(), None if bits is None else bits.data_ptr(),
-                                                          out.data_ptr(), lse2.data_ptr(), windows, n_win, n, heads, c3 // (3 * heads), float(scale),
-                                                          roi_attn._stream()), "transoar_win_attn_forward")
+        launch(lib.transoar_win_attn_forward, qkv, qkv.data_ptr(), bias_pad.data_ptr(), ptr(bits), out.data_ptr(), lse2.data_ptr(),
+               windows, n_win, n, heads, c3 // (3 * heads), float(scale))
         ctx.save_for_backward(qkv, out, lse2, bias_pad, bits)
         ctx.heads, ctx.scale = heads, float(scale)
         return out
@@ -67,11 +60,9 @@ class _WindowAttention(torch.autograd.Function):
         dout = dout.to(torch.bfloat16).contiguous()
         dqkv = torch.empty_like(qkv)
         dbias = torch.zeros_like(bias_pad)
-        with torch.cuda.device(qkv.device):
-            roi_attn._check(lib.transoar_win_attn_backward(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse2.data_ptr(), bias_pad.data_ptr(),
-                                                           None if bits is None else bits.data_ptr(), dqkv.data_ptr(), dbias.data_ptr(), windows,
-                                                           n_win, n, ctx.heads, c3 // (3 * ctx.heads), ctx.scale, roi_attn._stream()),
-                            "transoar_win_attn_backward")
+        launch(lib.transoar_win_attn_backward, qkv, qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse2.data_ptr(),
+               bias_pad.data_ptr(), ptr(bits), dqkv.data_ptr(), dbias.data_ptr(), windows,
+               n_win, n, ctx.heads, c3 // (3 * ctx.heads), ctx.scale)
         return dqkv, dbias[:, :, :n], None, None, None
 
 
