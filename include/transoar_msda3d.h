@@ -186,6 +186,33 @@ size_t transoar_msda3d_backward_workspace_bytes(int N, int S, int M, int C,
                                                 unsigned flags);
 
 /*
+ * Which kernels the entry points above would launch for these arguments.  Pure
+ * host arithmetic (no device is touched): the same plan the launches consume.
+ * Returns the entry points' error for bad dimensions / dtypes; otherwise what
+ * transoar_msda3d_backward (grad_proj = 0) or transoar_msda3d_backward_proj
+ * (grad_proj = 1) would return short of their pointer, alignment and workspace
+ * checks, i.e. TRANSOAR_OK or TRANSOAR_ERR_MODE.  plan[TRANSOAR_PLAN_FWD] is
+ * filled in both cases; the backward fields are -1 under TRANSOAR_ERR_MODE.
+ */
+enum {
+  TRANSOAR_PLAN_FWD = 0,           /* transoar_msda3d_forward: one of TRANSOAR_FWD_*                         */
+  TRANSOAR_PLAN_BWD_QUERY = 1,     /* grad_loc / grad_attn (or grad_proj) kernel: one of TRANSOAR_BWD_QUERY_* */
+  TRANSOAR_PLAN_BWD_VALUE = 2,     /* grad_value walk: one of TRANSOAR_BWD_VALUE_*                           */
+  TRANSOAR_PLAN_COARSE_FIRST = 3,  /* first level on the chunked cell walk; L when none or no tile walk      */
+  TRANSOAR_PLAN_FIELDS = 4
+};
+enum { TRANSOAR_FWD_GENERIC = 0, TRANSOAR_FWD_VEC = 1, TRANSOAR_FWD_BRICK = 2, TRANSOAR_FWD_MMA = 3,
+       TRANSOAR_FWD_PCM = 4, TRANSOAR_FWD_Q16 = 5 };
+enum { TRANSOAR_BWD_QUERY_GENERIC = 0, TRANSOAR_BWD_QUERY_VEC = 1, TRANSOAR_BWD_QUERY_BRICK = 2,
+       TRANSOAR_BWD_QUERY_MMA = 3, TRANSOAR_BWD_QUERY_MMA_DET = 4 };
+enum { TRANSOAR_BWD_VALUE_GENERIC = 0, TRANSOAR_BWD_VALUE_PULL = 1, TRANSOAR_BWD_VALUE_TILE_W8 = 2,
+       TRANSOAR_BWD_VALUE_TILE_MMA = 3 };
+int transoar_msda3d_plan(int N, int S, int M, int C, int L, int Lq, int P,
+                         int value_dtype, int loc_dtype,
+                         const int64_t* host_spatial_shapes, unsigned flags,
+                         int grad_proj, int* plan /* TRANSOAR_PLAN_FIELDS ints */);
+
+/*
  * Optional per-kernel timing (used by bench.py for the roofline figures).
  * While enabled, every kernel the two entry points launch is bracketed by a
  * HIP event pair recorded on the caller's stream.  transoar_msda3d_profile_read
@@ -212,7 +239,7 @@ int transoar_msda3d_profile_read(double* total_ms, long* launches);
 /* Human-readable text for a return code of the functions above. */
 const char* transoar_msda3d_strerror(int code);
 
-/* ABI version of this header: bumped on any signature change. */
+/* ABI version of this header (7: transoar_msda3d_plan): bumped on any signature change. */
 int transoar_msda3d_abi_version(void);
 
 #ifdef __cplusplus

@@ -79,6 +79,7 @@ def test_argument_errors_are_returned_not_printed():
     assert lib.transoar_msda3d_backward(p16, p16, p16, p16, p16, None, p16, p16, p16, None, 0, *dims_ok, 0, 0, None, 0, None) == -1
     assert lib.transoar_msda3d_backward(p16, p16, p16, p16, p16, p16, p16, p16, p16, None, 0, 2, 1000, 6, 64, 1, 10, 4, 0, 0, None, 0, None) == -6
     assert lib.transoar_msda3d_backward_workspace_bytes(2, 1000, 6, 64, 1, 10, 4, 0, 0, 0) > 0
+    assert lib.transoar_msda3d_plan(2, 1000, 6, 64, 1, 0, 4, 0, 0, None, 0, 0, (ctypes.c_int * 4)()) == -2     # Lq = 0
     for code in (0, -1, -2, -3, -4, -5, -6, -7):
         assert len(lib.transoar_msda3d_strerror(code)) > 0
 

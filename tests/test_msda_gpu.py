@@ -751,3 +751,72 @@ def test_module_head_gather_node_matches_two_node_path():
     assert torch.equal(grads[True]["out"], grads[False]["out"])
     for k in grads[False]:
         assert relerr(grads[True][k], grads[False][k]) <= 2.0 ** -6, k
+
+
+# ---------------------------------------------------------------------------
+# the host plan (transoar_msda3d_plan) against what is actually launched
+# ---------------------------------------------------------------------------
+PLAN_LEVELS = [(9, 6, 11), (5, 3, 6), (2, 2, 3)]
+_plan_cases = {}
+
+
+def _plan_case(Lq, vdt):
+    """Inputs on the host + the C oracle's results for them, computed once per (Lq, storage type)."""
+    if (Lq, vdt) not in _plan_cases:
+        shapes = torch.as_tensor(PLAN_LEVELS, dtype=torch.long)
+        lsi = level_starts(shapes)
+        value, loc, attn = rand_inputs(17, 2, 6, 64, Lq, 3, 4, shapes, torch.float32, -0.1, 1.1)
+        v = value.to(vdt)
+        go = torch.randn(2, Lq, 6 * 64, generator=torch.Generator().manual_seed(18)).to(vdt)
+        f = lambda t: t.float().numpy()
+        ref = (c_oracle.forward(f(v), shapes.numpy(), lsi.numpy(), f(loc), f(attn)),
+               *c_oracle.backward(f(v), shapes.numpy(), lsi.numpy(), f(loc), f(attn), f(go)))
+        _plan_cases[(Lq, vdt)] = (v, shapes, lsi, loc, attn, go, ref)
+    return _plan_cases[(Lq, vdt)]
+
+
+def _kinds_of_plan(fields, folded, L):
+    """The ProfScope kinds of transoar_amd/csrc/msda3d.hip that a plan implies (launch_fwd; BwdLaunch::run and its stages)."""
+    kinds = {"fwd_generic" if fields["fwd"] == 0 else "fwd"}
+    if fields["bwd_query"] == 0:
+        return kinds | {"bwd_generic"}
+    kinds |= {"bwd_query", "scan"}
+    if fields["bwd_query"] in (3, 4) or not folded:          # the matrix-core chain counts first; else only without host shapes
+        kinds.add("cell_count")
+    if fields["bwd_query"] != 3:                             # mma wrote the records itself; mma_det sorts and gathers them here
+        kinds.add("cell_fill")
+    if fields["bwd_value"] == 1:
+        return kinds | {"pull"}
+    return kinds | {"value_tile"} | ({"value_cells"} if fields["coarse_first"] < L else set())
+
+
+@pytest.mark.parametrize("name,flags,hint,Lq,vdt", [
+    ("defaults", 0, True, None, torch.bfloat16), ("no_mma", 16, True, None, torch.bfloat16),
+    ("no_brick", 4, True, None, torch.bfloat16), ("force_generic", 1, True, None, torch.bfloat16),
+    ("deterministic", 64, True, None, torch.bfloat16), ("no_host_shapes", 0, False, None, torch.bfloat16),
+    ("Lq50", 0, True, 50, torch.bfloat16), ("fp32", 0, True, None, torch.float32)])
+def test_plan_predicts_the_launched_kernels(MSDA, name, flags, hint, Lq, vdt):
+    """One forward and one backward with per-kernel profiling on: the kinds that were launched are exactly the kinds the
+    plan implies, and the results match the C oracle (a plan that launched the wrong kernel's arguments fails here)."""
+    from transoar_amd import _native
+    S = sum(d * h * w for d, h, w in PLAN_LEVELS)
+    v, shapes, lsi, loc, attn, go, ref = _plan_case(Lq or S, vdt)
+    dev = [t.cuda() for t in (v, shapes, lsi, loc, attn, go)]
+    MSDA.flags, MSDA.locality_hint = flags, hint
+    try:
+        status, fields = MSDA.plan(dev[0], dev[1], Lq or S, 4, torch.float32)
+        assert status == 0
+        _native.profile_enable(True)
+        _native.profile_read()
+        out = MSDA.ms_deform_attn_forward(*dev[:5], 64)
+        gv, gl, ga = MSDA.ms_deform_attn_backward(*dev, 64)
+        torch.cuda.synchronize()
+        launched = {k for k, (_, n) in _native.profile_read().items() if n > 0}
+    finally:
+        _native.profile_enable(False)
+        MSDA.flags, MSDA.locality_hint = 0, True
+    assert launched == _kinds_of_plan(fields, hint, len(PLAN_LEVELS)), (name, fields)
+    assert relerr(out, torch.from_numpy(ref[0])) <= TOL[vdt]
+    assert relerr(gv, torch.from_numpy(ref[1])) <= TOL[vdt]
+    assert relerr(gl, torch.from_numpy(ref[2])) <= 1e-4
+    assert relerr(ga, torch.from_numpy(ref[3])) <= 1e-4

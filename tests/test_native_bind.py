@@ -39,6 +39,7 @@ def test_every_type_of_the_headers_once():
     assert msda["transoar_msda3d_profile_enable"] == (None, [I])
     assert conv["transoar_conv3d_wgrad_part_floats"] == (L, [I] * 4)
     assert msda["transoar_msda3d_backward_workspace_bytes"] == (Z, [I] * 9 + [U])
+    assert msda["transoar_msda3d_plan"] == (I, [I] * 9 + [P, U, I, P])                                 # host pointers in and out
     assert msda["transoar_msda3d_abi_version"] == (I, [])
     # and they are what the loaded library carries
     fused = _native.lib.transoar_msda3d_forward_fused

@@ -24,7 +24,7 @@ _INCLUDE = os.path.join(os.path.dirname(_PKG), "include")
 
 F32, F64, BF16, F16 = 0, 1, 2, 3
 FORCE_GENERIC = 1
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class NativeLibraryError(ImportError):

@@ -3,6 +3,7 @@
 //   msda3d_gather.hpp   forward + grad_loc/grad_attn (query-stationary gathers)
 //   msda3d_scatter.hpp  grad_value (cell sort + voxel-stationary pull, no atomics)
 //   msda3d_generic.hpp  any-C / fp64 correctness kernels
+// Which of them run for a shape and flags is decided in msda3d_plan.hpp (host only).
 //
 // What is computed is fixed by the reference (semantics: SURVEY.md appendix A;
 // ops/src/cuda/ms_deform_im2col_cuda.cuh:31-114, 116-241, 370-439).  How is
@@ -22,6 +23,7 @@
 #include "msda3d_gather.hpp"
 #include "msda3d_generic.hpp"
 #include "msda3d_scatter.hpp"
+#include "msda3d_plan.hpp"
 
 #include <map>
 #include <mutex>
@@ -104,47 +106,10 @@ static inline hipError_t zero_async(void* p, size_t bytes, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------
-// host dispatch
+// host dispatch: WHICH kernels run is decided in msda3d_plan.hpp; below, a plan is obtained and launched
 // ---------------------------------------------------------------------------
-struct Dims { int N, S, M, C, L, Lq, P; };
-
-static inline int lpv_log2(int C, int elt) {
-  const long bytes = static_cast<long>(C) * elt;
-  if (bytes == 128) return 3;
-  if (bytes == 256) return 4;
-  if (bytes == 512) return 5;
-  return -1;
-}
-
-// Brick schedule from host-side level shapes (NULL -> linear order).  `rows` is what the
-// kernel's row index ranges over (S for voxel rows; Lq for queries, usable only when Lq == S,
-// i.e. the queries ARE the pyramid's voxels as in the refine block's self-attention).
-static BrickOrder make_order(const int64_t* host_shapes, const Dims& d, int rows) {
-  BrickOrder o{};
-  if (!host_shapes || rows != d.S) return o;
-  long start = 0, pad = 0;
-  for (int l = 0; l < d.L; ++l) {
-    const long D = host_shapes[3 * l], H = host_shapes[3 * l + 1], W = host_shapes[3 * l + 2];
-    if (D <= 0 || H <= 0 || W <= 0) return BrickOrder{};
-    o.D[l] = static_cast<int>(D); o.H[l] = static_cast<int>(H); o.W[l] = static_cast<int>(W);
-    o.start[l] = static_cast<int>(start);
-    o.nbh[l] = static_cast<int>((H + kBrickH - 1) / kBrickH);
-    o.nbw[l] = static_cast<int>((W + kBrickW - 1) / kBrickW);
-    o.pad_start[l] = static_cast<int>(pad);
-    pad += ((D + kBrickD - 1) / kBrickD) * o.nbh[l] * o.nbw[l] * kBrickSlots;
-    start += D * H * W;
-  }
-  if (start != d.S || pad * d.N * d.M >= (1L << 31)) return BrickOrder{};
-  o.pad_start[d.L] = static_cast<int>(pad);
-  o.L = d.L;
-  o.enabled = 1;
-  return o;
-}
-static inline long order_units(const BrickOrder& o, const Dims& d, int rows) {
-  return static_cast<long>(d.N) * d.M * (o.enabled ? o.pad_start[o.L] : rows);
-}
-
-static inline size_t align16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
+int sort_keys64(unsigned long long* keys, unsigned long long* alt, long n, int end_bit, void* temp, size_t* temp_bytes,
+                unsigned long long** sorted, hipStream_t st);          // msda3d_sort.hip
 
 // Launch constants of the brick-scheduled kernels (BrickOrder: ~300 bytes; CoarseLevels) live in device memory and
 // the kernels read them through a pointer: kernel arguments stay a handful of scalars and pointers, which is what
@@ -179,66 +144,6 @@ template <typename T> static const T* device_const(const T& v, hipStream_t st) {
   return static_cast<const T*>(device_const(&v, sizeof(T), st));
 }
 
-// Can the vector kernels run this problem?  (32-bit byte offsets into value,
-// 32-bit bin / point indices.)
-static inline int vec_lpv(const Dims& d, int elt, unsigned flags) {
-  if (flags & TRANSOAR_MSDA3D_FORCE_GENERIC) return -1;
-  const long value_bytes = static_cast<long>(d.N) * d.S * d.M * d.C * elt;
-  const long n_points = static_cast<long>(d.N) * d.Lq * d.M * d.L * d.P;
-  const long n_bins = static_cast<long>(d.N) * d.M * 8 * d.S;
-  if (value_bytes >= 0xfffffff0L || n_points >= (1L << 31) - 1 || n_bins >= (1L << 31) - 1) return -1;
-  // row index and row pitch go through the 24-bit multiplier
-  if (static_cast<long>(d.N) * d.S >= (1L << 24) || static_cast<long>(d.M) * d.C * elt >= (1L << 24)) return -1;
-  if (n_points * 32 >= 0xfffffff0L) return -1;   // record array addressed with 32-bit byte offsets
-  if (static_cast<long>(d.N) * d.Lq * d.M >= (1L << 24) ||
-      static_cast<long>(d.N) * d.Lq * d.M * d.C * elt >= 0x7ffffff0L) return -1;
-  return lpv_log2(d.C, elt);
-}
-
-struct BwdWorkspace {
-  size_t count, tile_sums, rank, rec_item, recs, coarse, det_keys, det_alt, det_temp, det_temp_bytes, total;
-  long n_bins, n_points, n_scan, n_tiles;
-};
-
-int sort_keys64(unsigned long long* keys, unsigned long long* alt, long n, int end_bit, void* temp, size_t* temp_bytes,
-                unsigned long long** sorted, hipStream_t st);          // msda3d_sort.hip
-
-static BwdWorkspace bwd_workspace(const Dims& d, size_t acc_size, unsigned flags = 0u) {
-  BwdWorkspace w;
-  w.n_points = static_cast<long>(d.N) * d.Lq * d.M * d.L * d.P;
-  w.n_bins = static_cast<long>(d.N) * d.M * 8 * d.S;   // (D+1)(H+1)(W+1) <= 8*D*H*W
-  w.n_scan = w.n_bins + 1;
-  w.n_tiles = (w.n_scan + kScanTile - 1) / kScanTile;
-  size_t off = 0;
-  w.count = off;     off += align16(sizeof(int) * w.n_scan);
-  w.tile_sums = off; off += align16(sizeof(int) * w.n_tiles);
-  w.rank = off;      off += align16(sizeof(int) * w.n_points);
-  w.rec_item = off;  off += align16(sizeof(int) * w.n_points);
-  w.recs = off;      off += align16(8 * acc_size * w.n_points);   // PointW8 (tile path) or PointRec
-  w.coarse = off;    off += align16(sizeof(float) * static_cast<size_t>(d.N) * d.S * d.M * d.C);   // fp32 rows of the coarse levels
-  w.det_keys = w.det_alt = w.det_temp = off;
-  w.det_temp_bytes = 0;
-  if (flags & TRANSOAR_MSDA3D_DETERMINISTIC) {      // two key buffers + the radix sort's scratch (histograms: a bound, checked at run time)
-    w.det_keys = off;  off += align16(sizeof(unsigned long long) * w.n_points);
-    w.det_alt = off;   off += align16(sizeof(unsigned long long) * w.n_points);
-    w.det_temp_bytes = align16((size_t(32) << 20) + static_cast<size_t>(w.n_points));
-    w.det_temp = off;  off += w.det_temp_bytes;
-  }
-  w.total = off;
-  return w;
-}
-
-// Does the point-column gather (msda3d_pcm.hpp) cover this problem?  Queries = voxels of a <= 4-level pyramid
-// known on the host, 64 channels, 4 points, every buffer addressable with 32-bit byte offsets.
-static bool pcm_ok(const BrickOrder& order, const Dims& d) {
-  if (!order.enabled || d.L > kPcmLevels || d.C != 64 || d.P != 4 || d.Lq != d.S) return false;
-  for (int l = 0; l < d.L; ++l)
-    if (order.D[l] > 1000 || order.H[l] > 1000 || order.W[l] > 1000) return false;
-  const long n_pts = static_cast<long>(d.N) * d.Lq * d.M * d.L * d.P;
-  const long n_wave = static_cast<long>(d.N) * (order.pad_start[order.L] >> 7) * d.M * 16;
-  const long vbytes = static_cast<long>(d.N) * d.S * d.M * d.C * 2;
-  return n_pts * 12 < 0xfffffff0L && n_wave < (1L << 31) - 8 && vbytes < 0xffffff00L;
-}
 static float host_bf16_round(float x) {
   unsigned u;
   memcpy(&u, &x, 4);
@@ -273,6 +178,8 @@ static Q16Const make_q16_const(const BrickOrder& order, int M) {
   }
   return c;
 }
+// LAUNCH(3 | 4 | 5): the vector kernels are templated on log2 of the lanes per value row
+#define TRANSOAR_BY_LG(LG, LAUNCH) do { if (LG == 3) LAUNCH(3); else if (LG == 4) LAUNCH(4); else LAUNCH(5); } while (0)
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return (v && *v) ? atoi(v) : dflt;
@@ -282,120 +189,89 @@ template <typename VT, typename LT>
 static int launch_fwd(const void* value, const int64_t* shapes, const int64_t* lsi,
                       const void* loc, const void* attn, void* out, const Dims& d,
                       const int64_t* host_shapes, unsigned flags, hipStream_t st) {
-  const long n_items = static_cast<long>(d.N) * d.Lq * d.M;
-  const BrickOrder order = make_order(host_shapes, d, d.Lq);
-  const long n_units = order_units(order, d, d.Lq);
-  const long n_blocks = ((order.enabled ? n_units : n_items) + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int lg = vec_lpv(d, sizeof(VT), flags);
+  const FwdPlan p = plan_fwd(d, sizeof(VT), sizeof(LT), host_shapes, flags);
+  const BrickOrder& order = p.order;
   const dim3 block(64 * kWavesPerBlock);
+  const dim3 wgrid(static_cast<unsigned>(((p.n_waves + 7) / 8) * 8));      // brick / mma / pcm: one workgroup or wave per p.n_waves
   auto v = static_cast<const VT*>(value);
   auto lo = static_cast<const LT*>(loc);
   auto at = static_cast<const LT*>(attn);
   auto o = static_cast<VT*>(out);
-  // LDS-tiled brick kernel: queries are the pyramid's voxels (Lq == S), host knows the shapes,
-  // 64 channels per head, 4 points per level (the refine block's configuration)
-  // (16-bit storage only: an fp32 box of the finest level does not fit the 48 KiB tile)
-  if constexpr (sizeof(VT) == 2) {
-    // matrix-core gather: one wave per 32 queries (2x4x4 sub-brick) and head
-    bool small = d.L <= kMmaLevels;
-    for (int l = 0; small && l < d.L; ++l) small = order.D[l] <= 1000 && order.H[l] <= 1000 && order.W[l] <= 1000;
-    // point-column form (msda3d_pcm.hpp): one wave per 8 queries (2x2x2 sub-brick) and head; fp32 locations
-    if constexpr (sizeof(LT) == 4) {
-      // 16 queries per wave (msda3d_q16.hpp, round 6): measured SLOWER than the 8-query kernel below;
-      // kept behind its flag as the carving's speed-of-light probe, parity-tested
-      if (lg >= 0 && small && pcm_ok(order, d) && (flags & TRANSOAR_MSDA3D_Q16) &&
-          !(flags & (TRANSOAR_MSDA3D_NO_BRICK | TRANSOAR_MSDA3D_NO_MMA | TRANSOAR_MSDA3D_MMA_Q32))) {
-        ProfScope prof(TRANSOAR_PROF_FWD, st);
+  ProfScope prof(p.kernel == TRANSOAR_FWD_GENERIC ? TRANSOAR_PROF_FWD_GENERIC : TRANSOAR_PROF_FWD, st);
+  switch (p.kernel) {
+    case TRANSOAR_FWD_GENERIC:
+      hipLaunchKernelGGL((msda3d_fwd_generic<VT, LT>), dim3((p.n_items + kWavesPerBlock - 1) / kWavesPerBlock),
+                         block, 0, st, v, shapes, lsi, lo, at, o, d.S, d.M, d.C, d.L, d.Lq, d.P, p.n_items);
+      break;
+    case TRANSOAR_FWD_VEC: {
+      const dim3 grid(((p.n_blocks + 7) / 8) * 8);
+#define TRANSOAR_FWD(LG)                                                                      \
+  hipLaunchKernelGGL((msda3d_fwd_vec<VT, LT, LG>), grid, block, 0, st, v, shapes, lsi, lo, at, \
+                     o, d.S, d.M, d.C, d.L, d.Lq, d.P, p.vbytes, p.n_units, p.n_blocks, order)
+      TRANSOAR_BY_LG(p.lg, TRANSOAR_FWD);
+#undef TRANSOAR_FWD
+      break;
+    }
+    case TRANSOAR_FWD_BRICK:       // LDS-tiled, per corner: one workgroup per brick and head
+      hipLaunchKernelGGL((msda3d_fwd_brick<VT, LT, 4, 64>), wgrid, dim3(kBrickThreads), kTileBytes, st, v, lo, at, o,
+                         d.S, d.M, d.L, p.n_waves, order);
+      break;
+    case TRANSOAR_FWD_MMA:         // matrix-core gather: one wave per 32 queries (2x4x4 sub-brick) and head
+      if constexpr (sizeof(VT) == 2) {
+        const BrickOrder* order_d = device_const(order, st);
+        if (order_d == nullptr) return TRANSOAR_ERR_CONST;
+        hipLaunchKernelGGL((msda3d_fwd_mma<VT, LT>), wgrid, dim3(64), 0, st, v, lo, at, o, d.S, d.M, d.L, p.vbytes,
+                           p.n_waves, order_d);
+      }
+      break;
+    case TRANSOAR_FWD_PCM:         // point-column form (msda3d_pcm.hpp): one wave per 8 queries (2x2x2 sub-brick) and head
+      if constexpr (sizeof(VT) == 2 && sizeof(LT) == 4) {
+        const PcmConst* cst = device_const(make_pcm_const(order), st);
+        if (cst == nullptr) return TRANSOAR_ERR_CONST;
+        hipLaunchKernelGGL((msda3d_fwd_pcm<VT, false>), wgrid, dim3(64), 0, st, v, lo, at, nullptr, nullptr, 0u, o,
+                           d.S, d.M, d.L, p.vbytes, static_cast<unsigned>(p.n_pts * 12), static_cast<unsigned>(p.n_pts * 4),
+                           static_cast<unsigned>(p.n_waves), cst);
+      }
+      break;
+    case TRANSOAR_FWD_Q16:         // 16 queries per wave (msda3d_q16.hpp); p.n_waves counts its units, `upw` of them per wave
+      if constexpr (sizeof(VT) == 2 && sizeof(LT) == 4) {
         static const int upw_env = env_int("TRANSOAR_MSDA3D_Q16_UPW", 4), probe = env_int("TRANSOAR_MSDA3D_Q16_PROBE", 0);
         const unsigned upw = static_cast<unsigned>(upw_env < 1 ? 1 : (upw_env > 64 ? 64 : upw_env));
-        const long n_units = static_cast<long>(d.N) * (order.pad_start[order.L] >> 7) * d.M * 8;
-        const long n_waves = (n_units + upw - 1) / upw;
-        const unsigned vbytes = static_cast<unsigned>(static_cast<long>(d.N) * d.S * d.M * d.C * sizeof(VT));
-        const long n_pts = static_cast<long>(d.N) * d.Lq * d.M * d.L * d.P;
+        const long n_waves = (p.n_waves + upw - 1) / upw;
         const Q16Const* cst = device_const(make_q16_const(order, d.M), st);
         if (cst == nullptr) return TRANSOAR_ERR_CONST;
         const dim3 grid(static_cast<unsigned>(((n_waves + 7) / 8) * 8));
 #define TRANSOAR_Q16(PROBE)                                                                                             \
-  hipLaunchKernelGGL((msda3d_fwd_q16<VT, PROBE>), grid, dim3(64), 0, st, v, lo, at, o, d.S, d.M, d.L, vbytes,               \
-                     static_cast<unsigned>(n_pts * 12), static_cast<unsigned>(n_pts * 4), static_cast<unsigned>(n_units), upw, cst)
+  hipLaunchKernelGGL((msda3d_fwd_q16<VT, PROBE>), grid, dim3(64), 0, st, v, lo, at, o, d.S, d.M, d.L, p.vbytes,           \
+                     static_cast<unsigned>(p.n_pts * 12), static_cast<unsigned>(p.n_pts * 4), static_cast<unsigned>(p.n_waves), upw, cst)
         if (probe == 1) TRANSOAR_Q16(1);
         else if (probe == 2) TRANSOAR_Q16(2);
         else if (probe == 3) TRANSOAR_Q16(3);
         else TRANSOAR_Q16(0);
 #undef TRANSOAR_Q16
-        return static_cast<int>(hipGetLastError());
       }
-      if (lg >= 0 && small && pcm_ok(order, d) &&
-          !(flags & (TRANSOAR_MSDA3D_NO_BRICK | TRANSOAR_MSDA3D_NO_MMA | TRANSOAR_MSDA3D_MMA_Q32))) {
-        ProfScope prof(TRANSOAR_PROF_FWD, st);
-        const long n_wave = static_cast<long>(d.N) * (order.pad_start[order.L] >> 7) * d.M * 16;
-        const unsigned vbytes = static_cast<unsigned>(static_cast<long>(d.N) * d.S * d.M * d.C * sizeof(VT));
-        const long n_pts = static_cast<long>(d.N) * d.Lq * d.M * d.L * d.P;
-        const PcmConst* cst = device_const(make_pcm_const(order), st);
-        if (cst == nullptr) return TRANSOAR_ERR_CONST;
-        hipLaunchKernelGGL((msda3d_fwd_pcm<VT, false>), dim3(static_cast<unsigned>(((n_wave + 7) / 8) * 8)), dim3(64), 0, st,
-                           v, lo, at, nullptr, nullptr, 0u, o, d.S, d.M, d.L, vbytes, static_cast<unsigned>(n_pts * 12),
-                           static_cast<unsigned>(n_pts * 4), static_cast<unsigned>(n_wave), cst);
-        return static_cast<int>(hipGetLastError());
-      }
-    }
-    if (lg >= 0 && order.enabled && small && d.C == 64 && d.P == 4 &&
-        !(flags & (TRANSOAR_MSDA3D_NO_BRICK | TRANSOAR_MSDA3D_NO_MMA))) {
-      ProfScope prof(TRANSOAR_PROF_FWD, st);
-      const long n_wave = static_cast<long>(d.N) * (order.pad_start[order.L] >> 7) * d.M * 4;
-      const unsigned vbytes = static_cast<unsigned>(static_cast<long>(d.N) * d.S * d.M * d.C * sizeof(VT));
-      const BrickOrder* order_d = device_const(order, st);
-      if (order_d == nullptr) return TRANSOAR_ERR_CONST;
-      hipLaunchKernelGGL((msda3d_fwd_mma<VT, LT>), dim3(static_cast<unsigned>(((n_wave + 7) / 8) * 8)), dim3(64), 0, st,
-                         v, lo, at, o, d.S, d.M, d.L, vbytes, n_wave, order_d);
-      return static_cast<int>(hipGetLastError());
-    }
-  }
-  if (lg >= 0 && order.enabled && d.C == 64 && d.P == 4 && sizeof(VT) == 2 && !(flags & TRANSOAR_MSDA3D_NO_BRICK)) {
-    ProfScope prof(TRANSOAR_PROF_FWD, st);
-    const long n_wg = static_cast<long>(d.N) * (order.pad_start[order.L] >> 7) * d.M;
-    const dim3 bgrid(((n_wg + 7) / 8) * 8);
-    hipLaunchKernelGGL((msda3d_fwd_brick<VT, LT, 4, 64>), bgrid, dim3(kBrickThreads), kTileBytes, st, v, lo, at, o,
-                       d.S, d.M, d.L, n_wg, order);
-    return static_cast<int>(hipGetLastError());
-  }
-  if (lg < 0) {
-    ProfScope prof(TRANSOAR_PROF_FWD_GENERIC, st);
-    hipLaunchKernelGGL((msda3d_fwd_generic<VT, LT>), dim3((n_items + kWavesPerBlock - 1) / kWavesPerBlock),
-                       block, 0, st, v, shapes, lsi, lo, at, o, d.S, d.M, d.C, d.L, d.Lq, d.P, n_items);
-  } else {
-    ProfScope prof(TRANSOAR_PROF_FWD, st);
-    const dim3 grid(((n_blocks + 7) / 8) * 8);
-    const unsigned vbytes = static_cast<unsigned>(static_cast<long>(d.N) * d.S * d.M * d.C * sizeof(VT));
-#define TRANSOAR_FWD(LG)                                                                      \
-  hipLaunchKernelGGL((msda3d_fwd_vec<VT, LT, LG>), grid, block, 0, st, v, shapes, lsi, lo, at, \
-                     o, d.S, d.M, d.C, d.L, d.Lq, d.P, vbytes, n_units, n_blocks, order)
-    if (lg == 3) TRANSOAR_FWD(3);
-    else if (lg == 4) TRANSOAR_FWD(4);
-    else TRANSOAR_FWD(5);
-#undef TRANSOAR_FWD
+      break;
   }
   return static_cast<int>(hipGetLastError());
 }
 
-// forward with the module's sampling head fused into the gather's prologue (msda3d_pcm.hpp, FUSED)
+// forward with the module's sampling head fused into the gather's prologue (msda3d_pcm.hpp, FUSED): covers a form
+// exactly when the plain forward (fp32 locations, no flags) takes the point-column kernel
 template <typename VT>
 static int launch_fwd_fused(const void* value, const void* proj, const float* ref, long ref_rows, void* out, const Dims& d,
                             const int64_t* host_shapes, hipStream_t st) {
-  const BrickOrder order = make_order(host_shapes, d, d.Lq);
-  if (vec_lpv(d, sizeof(VT), 0) < 0 || !pcm_ok(order, d)) return TRANSOAR_ERR_DIM;
+  const FwdPlan p = plan_fwd(d, sizeof(VT), sizeof(float), host_shapes, 0u);
+  if (p.kernel != TRANSOAR_FWD_PCM) return TRANSOAR_ERR_DIM;
   if (ref_rows != d.Lq && ref_rows != static_cast<long>(d.N) * d.Lq) return TRANSOAR_ERR_DIM;
   ProfScope prof(TRANSOAR_PROF_FWD, st);
-  const long n_wave = static_cast<long>(d.N) * (order.pad_start[order.L] >> 7) * d.M * 16;
-  const unsigned vbytes = static_cast<unsigned>(static_cast<long>(d.N) * d.S * d.M * d.C * sizeof(VT));
-  const PcmConst* cst = device_const(make_pcm_const(order), st);
+  const PcmConst* cst = device_const(make_pcm_const(p.order), st);
   if (cst == nullptr) return TRANSOAR_ERR_CONST;
   const unsigned ref_bstride = ref_rows == d.Lq ? 0u : static_cast<unsigned>(d.Lq) * d.L * 12u;
   const long proj_bytes = static_cast<long>(d.N) * d.S * 4 * d.M * d.L * d.P * 2;
-  hipLaunchKernelGGL((msda3d_fwd_pcm<VT, true>), dim3(static_cast<unsigned>(((n_wave + 7) / 8) * 8)), dim3(64), 0, st,
+  hipLaunchKernelGGL((msda3d_fwd_pcm<VT, true>), dim3(static_cast<unsigned>(((p.n_waves + 7) / 8) * 8)), dim3(64), 0, st,
                      static_cast<const VT*>(value), nullptr, nullptr, static_cast<const unsigned short*>(proj), ref, ref_bstride,
-                     static_cast<VT*>(out), d.S, d.M, d.L, vbytes, static_cast<unsigned>(proj_bytes),
-                     static_cast<unsigned>(ref_rows * d.L * 12), static_cast<unsigned>(n_wave), cst);
+                     static_cast<VT*>(out), d.S, d.M, d.L, p.vbytes, static_cast<unsigned>(proj_bytes),
+                     static_cast<unsigned>(ref_rows * d.L * 12), static_cast<unsigned>(p.n_waves), cst);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -409,231 +285,173 @@ __global__ __launch_bounds__(256) void msda3d_det_gather(const unsigned long lon
   recs[j] = slots[static_cast<unsigned>(k)];
 }
 
-template <typename VT, typename LT>
-static size_t bwd_workspace_bytes(const Dims& d, unsigned flags) {
-  using A = typename Elem<VT>::acc;
-  if (vec_lpv(d, sizeof(VT), flags) >= 0) return bwd_workspace(d, sizeof(A), flags).total;
-  // generic path: fp32 accumulator for 16-bit storage
-  return sizeof(VT) == 2 ? align16(sizeof(float) * static_cast<size_t>(d.N) * d.S * d.M * d.C) : 0;
-}
-
 #define TRANSOAR_CHECK_HIP(expr)                         \
   do {                                                   \
     const hipError_t e_ = (expr);                        \
     if (e_ != hipSuccess) return static_cast<int>(e_);   \
   } while (0)
 
+// One backward call: the plan, typed views of the caller's buffers and of the workspace regions, and the launch of
+// each stage.  run() is the whole sequence; no stage decides anything the plan has not decided.
 template <typename VT, typename LT>
-static int launch_bwd(const void* value, const int64_t* shapes, const int64_t* lsi,
-                      const void* loc, const void* attn, const void* grad_out, void* grad_value,
-                      void* grad_loc, void* grad_attn, void* workspace, size_t workspace_bytes,
-                      const Dims& d, const int64_t* host_shapes, unsigned flags, hipStream_t st, void* grad_proj = nullptr) {
+struct BwdLaunch {
   using A = typename Elem<VT>::acc;
-  if (workspace_bytes < bwd_workspace_bytes<VT, LT>(d, flags)) return TRANSOAR_ERR_WORKSPACE;
-  // grad_proj: the sampling head's backward folded into the query kernel (transoar_msda3d_backward_proj): only the
-  // matrix-core chain writes it
-  if (grad_proj != nullptr && (sizeof(VT) != 2 || sizeof(LT) != 4 || vec_lpv(d, sizeof(VT), flags) < 0)) return TRANSOAR_ERR_MODE;
-  const long n_items = static_cast<long>(d.N) * d.Lq * d.M;
-  const BrickOrder q_order = make_order(host_shapes, d, d.Lq);
-  const long q_units = order_units(q_order, d, d.Lq);
-  const long n_blocks = (q_units + kWavesPerBlock - 1) / kWavesPerBlock;
-  const int lg = vec_lpv(d, sizeof(VT), flags);
-  const dim3 block(64 * kWavesPerBlock);
-  auto v = static_cast<const VT*>(value);
-  auto lo = static_cast<const LT*>(loc);
-  auto at = static_cast<const LT*>(attn);
-  auto go = static_cast<const VT*>(grad_out);
-  auto gl = static_cast<LT*>(grad_loc);
-  auto ga = static_cast<LT*>(grad_attn);
-  const size_t value_elems = static_cast<size_t>(d.N) * d.S * d.M * d.C;
+  const Dims& d;
+  const BwdPlan& p;
+  hipStream_t st;
+  char* ws;
+  const int64_t *shapes, *lsi;
+  const VT *v, *go;
+  const LT *lo, *at;
+  VT* gv;
+  LT *gl, *ga;
+  unsigned short* gp;      // grad_proj (transoar_msda3d_backward_proj) or nullptr
+  bool fork;               // TRANSOAR_MSDA3D_FORK: the coarse walk of value_tile on the side stream
+  const dim3 block{64 * kWavesPerBlock};
+  const dim3 pgrid{static_cast<unsigned>((p.ws.n_points + 255) / 256)};        // one thread per sampling point
+  int* count = reinterpret_cast<int*>(ws + p.ws.count);
+  int* tile_sums = reinterpret_cast<int*>(ws + p.ws.tile_sums);
+  int* rank = reinterpret_cast<int*>(ws + p.ws.rank);
+  int* rec_item = reinterpret_cast<int*>(ws + p.ws.rec_item);
 
-  if (lg < 0) {
-    // scatter with fp atomics into a zeroed accumulator of type A
+  int run() const {
+    if (p.query == TRANSOAR_BWD_QUERY_GENERIC) return generic();
+    TRANSOAR_CHECK_HIP(zero_async(count, sizeof(int) * p.n_scan, st));
+    // 1. grad_loc / grad_attn (+ the binning pass of the point sort when folded)
+    if (p.sorted_by_query) {
+      if (const int rc = query_mma()) return rc;
+    } else {
+      ProfScope prof(TRANSOAR_PROF_BWD_QUERY, st);
+      if (p.query == TRANSOAR_BWD_QUERY_BRICK) {
+        if constexpr (sizeof(VT) == 2)
+          hipLaunchKernelGGL((msda3d_bwd_query_brick<VT, LT, 4, 64>), dim3(((p.q_waves + 7) / 8) * 8), dim3(kBrickThreads),
+                             kTileBytes, st, v, lo, at, go, gl, ga, count, rank, static_cast<int>(p.cells_per_slab), d.S, d.M,
+                             d.L, p.q_waves, p.q_order);
+      } else {
+        const dim3 grid(((p.q_blocks + 7) / 8) * 8);
+#define TRANSOAR_BWDQ(LG)                                                                   \
+  hipLaunchKernelGGL((msda3d_bwd_query_vec<VT, LT, LG>), grid, block, 0, st, v, shapes, lsi, lo, \
+                     at, go, gl, ga, p.fold_count ? count : nullptr, rank, static_cast<int>(p.cells_per_slab), \
+                     d.S, d.M, d.C, d.L, d.Lq, d.P, p.vbytes, p.q_units, p.q_blocks, p.q_order)
+        TRANSOAR_BY_LG(p.lg, TRANSOAR_BWDQ);
+#undef TRANSOAR_BWDQ
+      }
+    }
+    // 2. sort the sampling points by cell (the matrix-core chain has done all of it)
+    if (!p.fold_count) {
+      ProfScope prof(TRANSOAR_PROF_CELL_COUNT, st);
+      hipLaunchKernelGGL((msda3d_cell_count<LT, A>), pgrid, dim3(256), 0, st, lo, at, shapes, lsi, count,
+                         rank, d.M, d.L, d.Lq, d.P, p.ws.n_points);
+    }
+    if (!p.sorted_by_query) scan();
+    // 3. grad_value rows
+    return p.value == TRANSOAR_BWD_VALUE_PULL ? value_pull() : value_tile();
+  }
+
+  // scatter with fp atomics into a zeroed accumulator of type A
+  int generic() const {
     ProfScope prof(TRANSOAR_PROF_BWD_GENERIC, st);
-    A* gv = sizeof(VT) == 2 ? static_cast<A*>(workspace) : static_cast<A*>(grad_value);
-    TRANSOAR_CHECK_HIP(hipMemsetAsync(gv, 0, sizeof(A) * value_elems, st));
-    hipLaunchKernelGGL((msda3d_bwd_generic<VT, LT>), dim3((n_items + kWavesPerBlock - 1) / kWavesPerBlock),
-                       block, 0, st, v, shapes, lsi, lo, at, go, gv, gl, ga, d.S, d.M, d.C, d.L, d.Lq, d.P,
-                       n_items);
+    A* acc = sizeof(VT) == 2 ? reinterpret_cast<A*>(ws) : reinterpret_cast<A*>(gv);
+    TRANSOAR_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(A) * p.value_elems, st));
+    hipLaunchKernelGGL((msda3d_bwd_generic<VT, LT>), dim3((p.n_items + kWavesPerBlock - 1) / kWavesPerBlock),
+                       block, 0, st, v, shapes, lsi, lo, at, go, acc, gl, ga, d.S, d.M, d.C, d.L, d.Lq, d.P,
+                       p.n_items);
     if (sizeof(VT) == 2) {
-      const int cast_blocks = static_cast<int>(std::min<size_t>((value_elems + 255) / 256, 1 << 16));
+      const int cast_blocks = static_cast<int>(std::min<size_t>((p.value_elems + 255) / 256, 1 << 16));
       hipLaunchKernelGGL((msda3d_cast_rows<VT>), dim3(cast_blocks), dim3(256), 0, st,
-                         reinterpret_cast<const float*>(gv), static_cast<VT*>(grad_value),
-                         static_cast<long>(value_elems));
+                         reinterpret_cast<const float*>(acc), gv, static_cast<long>(p.value_elems));
     }
     return static_cast<int>(hipGetLastError());
   }
 
-  const dim3 grid(((n_blocks + 7) / 8) * 8);
-  const unsigned vbytes = static_cast<unsigned>(value_elems * sizeof(VT));
-  const BwdWorkspace w = bwd_workspace(d, sizeof(A), flags);
-  char* ws = static_cast<char*>(workspace);
-  int* count = reinterpret_cast<int*>(ws + w.count);
-  int* tile_sums = reinterpret_cast<int*>(ws + w.tile_sums);
-  int* rank = reinterpret_cast<int*>(ws + w.rank);
-  int* rec_item = reinterpret_cast<int*>(ws + w.rec_item);
-  auto recs = reinterpret_cast<PointRec<A>*>(ws + w.recs);
-  // cells per (batch, head) slab: needs the level shapes on the host; without them the binning
-  // runs as its own kernel (msda3d_cell_count) after the gather
-  long cells_per_slab = 0;
-  if (host_shapes)
-    for (int l = 0; l < d.L; ++l)
-      cells_per_slab += (host_shapes[3 * l] + 1) * (host_shapes[3 * l + 1] + 1) * (host_shapes[3 * l + 2] + 1);
-  const bool fold_count = host_shapes != nullptr && cells_per_slab * d.N * d.M <= w.n_bins;
-  // entries of the count / offset array that are in use: one per cell + the end of the last run (the upper bound
-  // n_bins + 1 = 8 S N M + 1 without host shapes: zeroing and scanning it was 45 MB four times over at the flagship size)
-  // (deterministic mode reads the walks' offsets one entry further on -- see below -- hence one more scanned entry)
-  const bool det_req = (flags & TRANSOAR_MSDA3D_DETERMINISTIC) != 0;
-  const long n_scan = fold_count ? cells_per_slab * d.N * d.M + 1 + (det_req && cells_per_slab * d.N * d.M + 2 <= w.n_scan ? 1 : 0) : w.n_scan;
-  const long n_tiles = (n_scan + kScanTile - 1) / kScanTile;
-  TRANSOAR_CHECK_HIP(zero_async(count, sizeof(int) * n_scan, st));
-  auto scan = [&]() {
+  void scan() const {
     ProfScope prof(TRANSOAR_PROF_SCAN, st);
-    hipLaunchKernelGGL(msda3d_scan_tiles, dim3(static_cast<unsigned>(n_tiles)), dim3(kScanThreads), 0,
-                       st, count, tile_sums, static_cast<int>(n_scan));
+    hipLaunchKernelGGL(msda3d_scan_tiles, dim3(static_cast<unsigned>(p.n_tiles)), dim3(kScanThreads), 0,
+                       st, count, tile_sums, static_cast<int>(p.n_scan));
     hipLaunchKernelGGL(msda3d_scan_tile_sums, dim3(1), dim3(kScanThreads), 0, st, tile_sums,
-                       static_cast<int>(n_tiles));
-    hipLaunchKernelGGL(msda3d_scan_add, dim3(static_cast<unsigned>(n_tiles)), dim3(kScanThreads), 0, st,
-                       count, tile_sums, static_cast<int>(n_scan));
-  };
+                       static_cast<int>(p.n_tiles));
+    hipLaunchKernelGGL(msda3d_scan_add, dim3(static_cast<unsigned>(p.n_tiles)), dim3(kScanThreads), 0, st,
+                       count, tile_sums, static_cast<int>(p.n_scan));
+  }
 
-  // 1. grad_loc / grad_attn (+ the binning pass of the point sort when folded)
-#define TRANSOAR_BWDQ(LG)                                                                   \
-  hipLaunchKernelGGL((msda3d_bwd_query_vec<VT, LT, LG>), grid, block, 0, st, v, shapes, lsi, lo, \
-                     at, go, gl, ga, fold_count ? count : nullptr, rank, static_cast<int>(cells_per_slab), \
-                     d.S, d.M, d.C, d.L, d.Lq, d.P, vbytes, q_units, n_blocks, q_order)
-  bool brick_done = false, recs_done = false, det = false;
-  if constexpr (sizeof(VT) == 2) {
-    bool small = d.L <= kMmaLevels;
-    for (int l = 0; small && l < d.L; ++l) small = q_order.D[l] <= 1000 && q_order.H[l] <= 1000 && q_order.W[l] <= 1000;
-    if (q_order.enabled && fold_count && small && d.C == 64 && d.P == 4 &&
-        !(flags & (TRANSOAR_MSDA3D_NO_BRICK | TRANSOAR_MSDA3D_NO_MMA))) {
-      // Matrix-core chain: count the points per cell (locations only), scan, then ONE kernel computes grad_loc /
-      // grad_attn and writes every point's 16-byte record at its sorted position.  The counts go to count[cell + 1]:
-      // after the exclusive scan that slot holds the first position of cell `cell` and serves as its cursor; when the
-      // records are written it has advanced to the first position of cell + 1, i.e. count[] is the offset array the
-      // grad_value walks read (offset[c], offset[c + 1]) without another pass.
-      const long n_wave = static_cast<long>(d.N) * (q_order.pad_start[q_order.L] >> 7) * d.M * 4;
-      const BrickOrder* order_d = device_const(q_order, st);
+  // Matrix-core chain: count the points per cell (locations only), scan, then ONE kernel computes grad_loc /
+  // grad_attn and writes every point's 16-byte record at its sorted position.  The counts go to count[cell + 1]:
+  // after the exclusive scan that slot holds the first position of cell `cell` and serves as its cursor; when the
+  // records are written it has advanced to the first position of cell + 1, i.e. count[] is the offset array the
+  // grad_value walks read (offset[c], offset[c + 1]) without another pass.
+  // Deterministic order (TRANSOAR_BWD_QUERY_MMA_DET): every point's record goes to its canonical slot (upper half of the record
+  // region) with the key (cell << 32 | slot); a stable radix sort of the keys (skipped points keep the all-ones key and
+  // end up last) and one gather put the records of a cell next to each other in slot order.  The exclusive scan of the
+  // counts is left as it is (no cursor advanced): count[c + 1] is the FIRST position of cell c, i.e. the walks
+  // read their (offset[c], offset[c + 1]) pairs from count + 1.
+  int query_mma() const {
+    if constexpr (sizeof(VT) == 2) {
+      const bool det = p.query == TRANSOAR_BWD_QUERY_MMA_DET;
+      const long n_wave = p.q_waves * 4, n_points = p.ws.n_points;
+      const BrickOrder* order_d = device_const(p.q_order, st);
       if (order_d == nullptr) return TRANSOAR_ERR_CONST;
       const dim3 qgrid(static_cast<unsigned>(((n_wave + 7) / 8) * 8));
       {
         ProfScope prof(TRANSOAR_PROF_CELL_COUNT, st);
         hipLaunchKernelGGL((msda3d_cell_count_mma<LT>), qgrid, dim3(64), 0, st, lo, count + 1,
-                           static_cast<int>(cells_per_slab), d.S, d.M, d.L, n_wave, order_d);
+                           static_cast<int>(p.cells_per_slab), d.S, d.M, d.L, n_wave, order_d);
       }
       scan();
-      det = det_req && cells_per_slab * d.N * d.M + 2 <= w.n_scan && w.n_points < (1L << 31);      // the sort takes the count as an int
-      if (det_req && !det) return TRANSOAR_ERR_MODE;
-      if (!det) {
+      PointR16* recs = reinterpret_cast<PointR16*>(ws + p.ws.recs);
+      PointR16* slots = det ? recs + n_points : recs;
+      auto keys = det ? reinterpret_cast<unsigned long long*>(ws + p.ws.det_keys) : nullptr;
+      auto alt = reinterpret_cast<unsigned long long*>(ws + p.ws.det_alt);
+      if (det) TRANSOAR_CHECK_HIP(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * n_points, st));
+      {
         ProfScope prof(TRANSOAR_PROF_BWD_QUERY, st);
         hipLaunchKernelGGL((msda3d_bwd_query_mma<VT, LT>), qgrid, dim3(64), 0, st,
-                           v, lo, at, go, gl, ga, count + 1, reinterpret_cast<PointR16*>(ws + w.recs), nullptr,
-                           static_cast<int>(cells_per_slab), d.S, d.M, d.L, vbytes, n_wave, order_d,
-                           static_cast<unsigned short*>(grad_proj));
-      } else {
-        // Deterministic order: every point's record goes to its canonical slot (upper half of the record region) with
-        // the key (cell << 32 | slot); a stable radix sort of the keys (skipped points keep the all-ones key and end up
-        // last) and one gather put the records of a cell next to each other in slot order.  The exclusive scan of the
-        // counts is left as it is (no cursor advanced): count[c + 1] is the FIRST position of cell c, i.e. the walks
-        // read their (offset[c], offset[c + 1]) pairs from count + 1.
-        auto keys = reinterpret_cast<unsigned long long*>(ws + w.det_keys);
-        auto alt = reinterpret_cast<unsigned long long*>(ws + w.det_alt);
-        PointR16* slots = reinterpret_cast<PointR16*>(ws + w.recs) + w.n_points;
-        TRANSOAR_CHECK_HIP(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * w.n_points, st));
-        {
-          ProfScope prof(TRANSOAR_PROF_BWD_QUERY, st);
-          hipLaunchKernelGGL((msda3d_bwd_query_mma<VT, LT>), qgrid, dim3(64), 0, st,
-                             v, lo, at, go, gl, ga, count + 1, slots, keys,
-                             static_cast<int>(cells_per_slab), d.S, d.M, d.L, vbytes, n_wave, order_d,
-                             static_cast<unsigned short*>(grad_proj));
-        }
-        ProfScope prof(TRANSOAR_PROF_CELL_FILL, st);
-        int cell_bits = 1;
-        while ((cells_per_slab * d.N * d.M) >> cell_bits) ++cell_bits;
-        size_t need = 0;
-        int rc = sort_keys64(keys, alt, w.n_points, 32 + cell_bits, nullptr, &need, nullptr, st);
-        if (rc != 0) return rc;
-        if (need > w.det_temp_bytes) return TRANSOAR_ERR_WORKSPACE;
-        unsigned long long* sorted = nullptr;
-        size_t temp_bytes = w.det_temp_bytes;
-        rc = sort_keys64(keys, alt, w.n_points, 32 + cell_bits, ws + w.det_temp, &temp_bytes, &sorted, st);
-        if (rc != 0) return rc;
-        hipLaunchKernelGGL(msda3d_det_gather, dim3(static_cast<unsigned>((w.n_points + 255) / 256)), dim3(256), 0, st,
-                           sorted, slots, reinterpret_cast<PointR16*>(ws + w.recs), w.n_points);
+                           v, lo, at, go, gl, ga, count + 1, slots, keys,
+                           static_cast<int>(p.cells_per_slab), d.S, d.M, d.L, p.vbytes, n_wave, order_d, gp);
       }
-      brick_done = recs_done = true;
+      if (!det) return TRANSOAR_OK;
+      ProfScope prof(TRANSOAR_PROF_CELL_FILL, st);
+      int cell_bits = 1;
+      while ((p.cells_per_slab * d.N * d.M) >> cell_bits) ++cell_bits;
+      size_t need = 0;
+      int rc = sort_keys64(keys, alt, n_points, 32 + cell_bits, nullptr, &need, nullptr, st);
+      if (rc != 0) return rc;
+      if (need > p.ws.det_temp_bytes) return TRANSOAR_ERR_WORKSPACE;
+      unsigned long long* sorted = nullptr;
+      size_t temp_bytes = p.ws.det_temp_bytes;
+      rc = sort_keys64(keys, alt, n_points, 32 + cell_bits, ws + p.ws.det_temp, &temp_bytes, &sorted, st);
+      if (rc != 0) return rc;
+      hipLaunchKernelGGL(msda3d_det_gather, dim3(static_cast<unsigned>((n_points + 255) / 256)), dim3(256), 0, st,
+                         sorted, slots, recs, n_points);
     }
+    return TRANSOAR_OK;
   }
-  if (det_req && !det) return TRANSOAR_ERR_MODE;           // no silent fall-back to an order that depends on atomics
-  if (grad_proj != nullptr && !recs_done) return TRANSOAR_ERR_MODE;      // the other query kernels write grad_loc / grad_attn
-  if constexpr (sizeof(VT) == 2) {
-    if (!brick_done && q_order.enabled && fold_count && d.C == 64 && d.P == 4 && !(flags & TRANSOAR_MSDA3D_NO_BRICK)) {
-      ProfScope prof(TRANSOAR_PROF_BWD_QUERY, st);
-      const long n_wg = static_cast<long>(d.N) * (q_order.pad_start[q_order.L] >> 7) * d.M;
-      hipLaunchKernelGGL((msda3d_bwd_query_brick<VT, LT, 4, 64>), dim3(((n_wg + 7) / 8) * 8), dim3(kBrickThreads),
-                         kTileBytes, st, v, lo, at, go, gl, ga, count, rank, static_cast<int>(cells_per_slab), d.S, d.M,
-                         d.L, n_wg, q_order);
-      brick_done = true;
-    }
-  }
-  if (!brick_done) {
-    ProfScope prof(TRANSOAR_PROF_BWD_QUERY, st);
-    if (lg == 3) TRANSOAR_BWDQ(3);
-    else if (lg == 4) TRANSOAR_BWDQ(4);
-    else TRANSOAR_BWDQ(5);
-  }
-#undef TRANSOAR_BWDQ
 
-  // 2. sort the sampling points by cell
-  const dim3 pgrid(static_cast<unsigned>((w.n_points + 255) / 256));
-  if (!fold_count) {
-    ProfScope prof(TRANSOAR_PROF_CELL_COUNT, st);
-    hipLaunchKernelGGL((msda3d_cell_count<LT, A>), pgrid, dim3(256), 0, st, lo, at, shapes, lsi, count,
-                       rank, d.M, d.L, d.Lq, d.P, w.n_points);
-  }
-  if (!recs_done) scan();
-  BrickOrder r_order = make_order(host_shapes, d, d.S);
-  if constexpr (sizeof(A) == 4) {
-    // brick-owner schedule: fp32 LDS tile per 4x4x8 brick, 8-weight point records
-    if (r_order.enabled && fold_count && d.C == kTileC && !(flags & TRANSOAR_MSDA3D_NO_BRICK)) {
-      auto recs8 = reinterpret_cast<PointW8<float>*>(ws + w.recs);
-      auto recs4 = reinterpret_cast<PointR16*>(ws + w.recs);       // matrix-core walks: 16 bytes with the row index inside
-      bool mma = false;
-      if constexpr (sizeof(VT) == 2) mma = !(flags & TRANSOAR_MSDA3D_NO_MMA);
-      if (!recs_done) {
+  // brick-owner schedule: fp32 LDS tile per 4x4x8 brick for the fine levels, chunked cell walk for the coarse ones
+  int value_tile() const {
+    if constexpr (sizeof(A) == 4) {
+      const bool mma = p.value == TRANSOAR_BWD_VALUE_TILE_MMA;
+      const CoarseLevels& cl = p.coarse;
+      const int cells = static_cast<int>(p.cells_per_slab), fine_bricks = p.fine_bricks, coarse_levels = d.L - cl.first;
+      auto recs8 = reinterpret_cast<PointW8<float>*>(ws + p.ws.recs);
+      auto recs4 = reinterpret_cast<PointR16*>(ws + p.ws.recs);       // matrix-core walks: 16 bytes with the row index inside
+      if (!p.sorted_by_query) {
         ProfScope prof(TRANSOAR_PROF_CELL_FILL, st);
         if (mma)
           hipLaunchKernelGGL((msda3d_cell_fill_r16<LT>), pgrid, dim3(256), 0, st, lo, at, shapes, lsi, count, rank, recs4,
-                             d.M, d.L, d.Lq, d.P, w.n_points);
+                             d.M, d.L, d.Lq, d.P, p.ws.n_points);
         else
           hipLaunchKernelGGL((msda3d_cell_fill_w8<LT, float>), pgrid, dim3(256), 0, st, lo, at, shapes, lsi, count,
-                             rank, recs8, rec_item, d.M, d.L, d.Lq, d.P, w.n_points);
+                             rank, recs8, rec_item, d.M, d.L, d.Lq, d.P, p.ws.n_points);
       }
-      // levels whose voxels receive >= kCoarsePointsPerVoxel points each go to the chunked walk
-      CoarseLevels cl{d.L, static_cast<int>(cells_per_slab), d.S, 0, 0};
-      const int* offsets = det ? count + 1 : count;
-      for (int l = d.L - 1; l >= 0 && !det; --l) {          // deterministic mode: no coarse level (their walk flushes with fp32 atomics)
-        const long vox = host_shapes[3 * l] * host_shapes[3 * l + 1] * host_shapes[3 * l + 2];
-        if (static_cast<long>(d.Lq) * d.P < kCoarsePointsPerVoxel * vox) break;
-        cl.first = l;
-        cl.cell_start -= static_cast<int>((host_shapes[3 * l] + 1) * (host_shapes[3 * l + 1] + 1) * (host_shapes[3 * l + 2] + 1));
-        cl.row_start = r_order.start[l];
-      }
-      cl.rows = d.S - cl.row_start;
-      const int coarse_levels = d.L - cl.first;
-      const int cell_chunk = mma ? kCmCellChunk : kCellChunk;
-      cl.chunks_per_slab = static_cast<int>((static_cast<long>(d.Lq) * d.P * coarse_levels + cell_chunk - 1) / cell_chunk) + 1;
-      const int fine_bricks = r_order.pad_start[cl.first] >> 7;
-      const BrickOrder* r_order_d = device_const(r_order, st);
+      const int* offsets = p.query == TRANSOAR_BWD_QUERY_MMA_DET ? count + 1 : count;
+      const BrickOrder* r_order_d = device_const(p.r_order, st);
       const CoarseLevels* cl_d = device_const(cl, st);
       if (r_order_d == nullptr || cl_d == nullptr) return TRANSOAR_ERR_CONST;
-      float* scratch = reinterpret_cast<float*>(ws + w.coarse);
+      float* scratch = reinterpret_cast<float*>(ws + p.ws.coarse);
       const long scratch_elems = static_cast<long>(d.N) * cl.rows * d.M * kTileC;
       // opt-in (TRANSOAR_MSDA3D_FORK): 3.90 -> 3.59 ms per eager backward at the flagship, but 1.1 ms per
       // step SLOWER when the step is replayed as a HIP graph (fork/join nodes), which is how bench.py runs
-      SideStream* side = (g_prof_on || !(flags & TRANSOAR_MSDA3D_FORK) || coarse_levels == 0 || fine_bricks == 0)
-                             ? nullptr : side_stream();
+      SideStream* side = (g_prof_on || !fork || coarse_levels == 0 || fine_bricks == 0) ? nullptr : side_stream();
       hipStream_t cst = st;
       if (side != nullptr) {
         TRANSOAR_CHECK_HIP(hipEventRecord(side->fork, st));
@@ -647,12 +465,10 @@ static int launch_bwd(const void* value, const int64_t* shapes, const int64_t* l
         if (mma) {
           if constexpr (sizeof(VT) == 2)       // 16 sorted points per MFMA K-step (msda3d_cells_mma.hpp)
             hipLaunchKernelGGL((msda3d_bwd_value_cells_mma<VT>), dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0,
-                               cst, go, offsets, recs4, scratch, static_cast<int>(cells_per_slab), d.N * d.M, d.M,
-                               cl_d, r_order_d);
+                               cst, go, offsets, recs4, scratch, cells, d.N * d.M, d.M, cl_d, r_order_d);
         } else {
           hipLaunchKernelGGL((msda3d_bwd_value_cells<VT>), dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, cst,
-                             go, count, recs8, rec_item, scratch, static_cast<int>(cells_per_slab), d.N * d.M, d.M, cl_d,
-                             r_order_d);
+                             go, count, recs8, rec_item, scratch, cells, d.N * d.M, d.M, cl_d, r_order_d);
         }
       }
       if (side != nullptr) TRANSOAR_CHECK_HIP(hipEventRecord(side->join, side->stream));
@@ -662,46 +478,58 @@ static int launch_bwd(const void* value, const int64_t* shapes, const int64_t* l
         if (mma) {
           if constexpr (sizeof(VT) == 2)
             hipLaunchKernelGGL((msda3d_bwd_value_tile_mma<VT>), dim3(static_cast<unsigned>(n_wg)), dim3(kBrickThreads), 0, st,
-                               go, offsets, recs4, static_cast<VT*>(grad_value), static_cast<int>(cells_per_slab),
-                               d.S, d.M, fine_bricks, n_wg, r_order_d);
+                               go, offsets, recs4, gv, cells, d.S, d.M, fine_bricks, n_wg, r_order_d);
         } else {
           hipLaunchKernelGGL((msda3d_bwd_value_tile<VT>), dim3(static_cast<unsigned>(n_wg)), dim3(kBrickThreads), 0, st, go,
-                             count, recs8, rec_item, static_cast<VT*>(grad_value), static_cast<int>(cells_per_slab),
-                             d.S, d.M, fine_bricks, n_wg, r_order_d);
+                             count, recs8, rec_item, gv, cells, d.S, d.M, fine_bricks, n_wg, r_order_d);
         }
       }
       if (side != nullptr) TRANSOAR_CHECK_HIP(hipStreamWaitEvent(st, side->join, 0));
       if (coarse_levels > 0) {
         const long n4 = scratch_elems / 4;
         hipLaunchKernelGGL((msda3d_coarse_rows_store<VT>), dim3(static_cast<unsigned>((n4 + 255) / 256)), dim3(256), 0, st,
-                           scratch, static_cast<VT*>(grad_value), d.S, d.M, cl.rows, cl.row_start, n4);
+                           scratch, gv, d.S, d.M, cl.rows, cl.row_start, n4);
       }
-      return static_cast<int>(hipGetLastError());
     }
-  }
-  {
-    ProfScope prof(TRANSOAR_PROF_CELL_FILL, st);
-    hipLaunchKernelGGL((msda3d_cell_fill<LT, A>), pgrid, dim3(256), 0, st, lo, at, shapes, lsi, count,
-                       rank, recs, rec_item, d.M, d.L, d.Lq, d.P, w.n_points);
+    return static_cast<int>(hipGetLastError());
   }
 
-  // 3. grad_value rows
-  if (r_order.enabled && (flags & TRANSOAR_MSDA3D_PULL_HEAD_MAJOR)) r_order.enabled = 2;
-  const long n_rows = order_units(r_order, d, d.S);
-  const long r_blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
-  const dim3 rgrid(((r_blocks + 7) / 8) * 8);
+  // voxel-stationary pull over PointRec records
+  int value_pull() const {
+    auto recs = reinterpret_cast<PointRec<A>*>(ws + p.ws.recs);
+    {
+      ProfScope prof(TRANSOAR_PROF_CELL_FILL, st);
+      hipLaunchKernelGGL((msda3d_cell_fill<LT, A>), pgrid, dim3(256), 0, st, lo, at, shapes, lsi, count,
+                         rank, recs, rec_item, d.M, d.L, d.Lq, d.P, p.ws.n_points);
+    }
+    const long n_rows = order_units(p.r_order, d, d.S);
+    const long r_blocks = (n_rows + kWavesPerBlock - 1) / kWavesPerBlock;
+    const dim3 rgrid(((r_blocks + 7) / 8) * 8);
 #define TRANSOAR_PULL(LG)                                                                        \
   hipLaunchKernelGGL((msda3d_bwd_value_pull<VT, A, LG>), rgrid, block, 0, st, go, shapes, lsi, count, \
-                     recs, rec_item, static_cast<VT*>(grad_value), d.S, d.M, d.C, d.L, n_rows, r_blocks, r_order, \
-                     static_cast<unsigned>(w.n_points * 4 * sizeof(A)))
-  {
+                     recs, rec_item, gv, d.S, d.M, d.C, d.L, n_rows, r_blocks, p.r_order, \
+                     static_cast<unsigned>(p.ws.n_points * 4 * sizeof(A)))
     ProfScope prof(TRANSOAR_PROF_PULL, st);
-    if (lg == 3) TRANSOAR_PULL(3);
-    else if (lg == 4) TRANSOAR_PULL(4);
-    else TRANSOAR_PULL(5);
-  }
+    TRANSOAR_BY_LG(p.lg, TRANSOAR_PULL);
 #undef TRANSOAR_PULL
-  return static_cast<int>(hipGetLastError());
+    return static_cast<int>(hipGetLastError());
+  }
+};
+
+template <typename VT, typename LT>
+static int launch_bwd(const void* value, const int64_t* shapes, const int64_t* lsi, const void* loc, const void* attn,
+                      const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, void* grad_proj,
+                      void* workspace, size_t workspace_bytes, const Dims& d, const int64_t* host_shapes, unsigned flags,
+                      hipStream_t st) {
+  // grad_proj: the sampling head's backward folded into the query kernel (transoar_msda3d_backward_proj)
+  const BwdPlan p = plan_bwd(d, sizeof(VT), sizeof(LT), host_shapes, flags, grad_proj != nullptr);
+  if (workspace_bytes < p.ws.total) return TRANSOAR_ERR_WORKSPACE;
+  if (p.status != TRANSOAR_OK) return p.status;          // refused before anything is launched
+  const BwdLaunch<VT, LT> c{d, p, st, static_cast<char*>(workspace), shapes, lsi, static_cast<const VT*>(value),
+                            static_cast<const VT*>(grad_out), static_cast<const LT*>(loc), static_cast<const LT*>(attn),
+                            static_cast<VT*>(grad_value), static_cast<LT*>(grad_loc), static_cast<LT*>(grad_attn),
+                            static_cast<unsigned short*>(grad_proj), (flags & TRANSOAR_MSDA3D_FORK) != 0};
+  return c.run();
 }
 
 static int check_common(const Dims& d, int value_dtype, int loc_dtype) {
@@ -717,6 +545,7 @@ static int check_common(const Dims& d, int value_dtype, int loc_dtype) {
   return TRANSOAR_OK;
 }
 
+static inline int elt_size(int dtype) { return dtype == TRANSOAR_F32 ? 4 : dtype == TRANSOAR_F64 ? 8 : 2; }
 static inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 }  // namespace transoar
@@ -766,58 +595,48 @@ extern "C" int transoar_msda3d_forward_fused(const void* value, const void* proj
   return launch_fwd_fused<f16_t>(value, proj, ref, ref_rows, out, d, host_spatial_shapes, st);
 }
 
-extern "C" int transoar_msda3d_backward(const void* value, const int64_t* spatial_shapes,
-                                        const int64_t* level_start_index, const void* sampling_loc,
-                                        const void* attn_weight, const void* grad_out,
-                                        void* grad_value, void* grad_sampling_loc,
-                                        void* grad_attn_weight, void* workspace,
-                                        size_t workspace_bytes, int N, int S, int M, int C, int L,
-                                        int Lq, int P, int value_dtype, int loc_dtype,
-                                        const int64_t* host_spatial_shapes, unsigned flags,
-                                        void* hip_stream) {
-  if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight ||
-      !grad_out || !grad_value || !grad_sampling_loc || !grad_attn_weight)
+// what the two backward entry points share; grad_proj != NULL: transoar_msda3d_backward_proj (no grad_loc / grad_attn)
+static int backward_entry(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                          const void* sampling_loc, const void* attn_weight, const void* grad_out, void* grad_value,
+                          void* grad_loc, void* grad_attn, void* grad_proj, void* workspace, size_t workspace_bytes,
+                          const Dims& d, int value_dtype, int loc_dtype, const int64_t* host_shapes, unsigned flags,
+                          void* hip_stream) {
+  if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !grad_out || !grad_value ||
+      (!grad_proj && (!grad_loc || !grad_attn)))
     return TRANSOAR_ERR_NULL;
-  const Dims d{N, S, M, C, L, Lq, P};
   const int rc = check_common(d, value_dtype, loc_dtype);
   if (rc != TRANSOAR_OK) return rc;
-  if (misaligned(value) || misaligned(sampling_loc) || misaligned(attn_weight) ||
-      misaligned(grad_out) || misaligned(grad_value) || misaligned(grad_sampling_loc) ||
-      misaligned(grad_attn_weight) || misaligned(workspace))
+  if (grad_proj && !proj_form(d, elt_size(value_dtype), elt_size(loc_dtype))) return TRANSOAR_ERR_MODE;
+  if (misaligned(value) || misaligned(sampling_loc) || misaligned(attn_weight) || misaligned(grad_out) ||
+      misaligned(grad_value) || misaligned(grad_loc) || misaligned(grad_attn) || misaligned(grad_proj) || misaligned(workspace))
     return TRANSOAR_ERR_ALIGN;
   if (!workspace && workspace_bytes != 0) return TRANSOAR_ERR_NULL;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   TRANSOAR_DISPATCH(value_dtype, loc_dtype,
-                    (launch_bwd<VT, LT>(value, spatial_shapes, level_start_index, sampling_loc,
-                                        attn_weight, grad_out, grad_value, grad_sampling_loc,
-                                        grad_attn_weight, workspace, workspace_bytes, d,
-                                        host_spatial_shapes, flags, st)));
+                    (launch_bwd<VT, LT>(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out,
+                                        grad_value, grad_loc, grad_attn, grad_proj, workspace, workspace_bytes, d,
+                                        host_shapes, flags, st)));
 }
 
-extern "C" int transoar_msda3d_backward_proj(const void* value, const int64_t* spatial_shapes,
-                                             const int64_t* level_start_index, const void* sampling_loc,
-                                             const void* attn_weight, const void* grad_out,
-                                             void* grad_value, void* grad_proj, void* workspace,
-                                             size_t workspace_bytes, int N, int S, int M, int C, int L,
-                                             int Lq, int P, int value_dtype, int loc_dtype,
-                                             const int64_t* host_spatial_shapes, unsigned flags,
-                                             void* hip_stream) {
-  if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight ||
-      !grad_out || !grad_value || !grad_proj)
-    return TRANSOAR_ERR_NULL;
-  const Dims d{N, S, M, C, L, Lq, P};
-  const int rc = check_common(d, value_dtype, loc_dtype);
-  if (rc != TRANSOAR_OK) return rc;
-  if (loc_dtype != TRANSOAR_F32 || (value_dtype != TRANSOAR_BF16 && value_dtype != TRANSOAR_F16) || L * P != 16) return TRANSOAR_ERR_MODE;
-  if (misaligned(value) || misaligned(sampling_loc) || misaligned(attn_weight) ||
-      misaligned(grad_out) || misaligned(grad_value) || misaligned(grad_proj) || misaligned(workspace))
-    return TRANSOAR_ERR_ALIGN;
-  if (!workspace && workspace_bytes != 0) return TRANSOAR_ERR_NULL;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  TRANSOAR_DISPATCH(value_dtype, loc_dtype,
-                    (launch_bwd<VT, LT>(value, spatial_shapes, level_start_index, sampling_loc,
-                                        attn_weight, grad_out, grad_value, nullptr, nullptr, workspace, workspace_bytes, d,
-                                        host_spatial_shapes, flags, st, grad_proj)));
+extern "C" int transoar_msda3d_backward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                        const void* sampling_loc, const void* attn_weight, const void* grad_out,
+                                        void* grad_value, void* grad_sampling_loc, void* grad_attn_weight, void* workspace,
+                                        size_t workspace_bytes, int N, int S, int M, int C, int L, int Lq, int P,
+                                        int value_dtype, int loc_dtype, const int64_t* host_spatial_shapes, unsigned flags,
+                                        void* hip_stream) {
+  return backward_entry(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
+                        grad_sampling_loc, grad_attn_weight, nullptr, workspace, workspace_bytes, Dims{N, S, M, C, L, Lq, P},
+                        value_dtype, loc_dtype, host_spatial_shapes, flags, hip_stream);
+}
+
+extern "C" int transoar_msda3d_backward_proj(const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                             const void* sampling_loc, const void* attn_weight, const void* grad_out,
+                                             void* grad_value, void* grad_proj, void* workspace, size_t workspace_bytes,
+                                             int N, int S, int M, int C, int L, int Lq, int P, int value_dtype, int loc_dtype,
+                                             const int64_t* host_spatial_shapes, unsigned flags, void* hip_stream) {
+  return backward_entry(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
+                        nullptr, nullptr, grad_proj, workspace, workspace_bytes, Dims{N, S, M, C, L, Lq, P},
+                        value_dtype, loc_dtype, host_spatial_shapes, flags, hip_stream);
 }
 
 extern "C" size_t transoar_msda3d_backward_workspace_bytes(int N, int S, int M, int C, int L, int Lq,
@@ -825,7 +644,23 @@ extern "C" size_t transoar_msda3d_backward_workspace_bytes(int N, int S, int M, 
                                                            unsigned flags) {
   const Dims d{N, S, M, C, L, Lq, P};
   if (check_common(d, value_dtype, loc_dtype) != TRANSOAR_OK) return 0;
-  TRANSOAR_DISPATCH(value_dtype, loc_dtype, (bwd_workspace_bytes<VT, LT>(d, flags)));
+  return plan_bwd(d, elt_size(value_dtype), elt_size(loc_dtype), nullptr, flags, false).ws.total;
+}
+
+extern "C" int transoar_msda3d_plan(int N, int S, int M, int C, int L, int Lq, int P, int value_dtype, int loc_dtype,
+                                    const int64_t* host_spatial_shapes, unsigned flags, int grad_proj, int* plan) {
+  if (!plan) return TRANSOAR_ERR_NULL;
+  const Dims d{N, S, M, C, L, Lq, P};
+  const int rc = check_common(d, value_dtype, loc_dtype);
+  if (rc != TRANSOAR_OK) return rc;
+  const int vs = elt_size(value_dtype), ls = elt_size(loc_dtype);
+  const BwdPlan b = plan_bwd(d, vs, ls, host_spatial_shapes, flags, grad_proj != 0);
+  const bool ok = b.status == TRANSOAR_OK;
+  plan[TRANSOAR_PLAN_FWD] = plan_fwd(d, vs, ls, host_spatial_shapes, flags).kernel;
+  plan[TRANSOAR_PLAN_BWD_QUERY] = ok ? b.query : -1;
+  plan[TRANSOAR_PLAN_BWD_VALUE] = ok ? b.value : -1;
+  plan[TRANSOAR_PLAN_COARSE_FIRST] = ok ? b.coarse.first : -1;
+  return b.status;
 }
 
 extern "C" const char* transoar_msda3d_strerror(int code) {
@@ -872,4 +707,4 @@ extern "C" int transoar_msda3d_profile_read(double* total_ms, long* launches) {
   return rc;
 }
 
-extern "C" int transoar_msda3d_abi_version(void) { return 6; }
+extern "C" int transoar_msda3d_abi_version(void) { return 7; }

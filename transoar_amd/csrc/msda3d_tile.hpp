@@ -198,7 +198,6 @@ __global__ __launch_bounds__(kBrickThreads) void msda3d_bwd_value_tile(
 // exactly once.  msda3d_coarse_rows_store then writes the rows in the storage type.
 // ---------------------------------------------------------------------------
 constexpr int kCellChunk = 256;
-constexpr long kCoarsePointsPerVoxel = 32;   // measured: 128 -> 32 moves level 1 of the flagship pyramid here (2.00 -> 1.90 ms serial)
 
 struct CoarseLevels {
   int first;             // first coarse level (levels first..L-1)

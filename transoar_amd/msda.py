@@ -122,7 +122,7 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     return out
 
 
-def ms_deform_attn_forward_fused(value, spatial_shapes, proj, reference_points, strict=True):
+def ms_deform_attn_forward_fused(value, spatial_shapes, proj, reference_points):
     """Gather with the module's sampling head in its prologue (no reference counterpart as one call: it is
     ops/modules/ms_deform_attn.py:114-136 -- softmax, ``ref + offsets / (W, H, D)``, MSDeformAttnFunction -- without
     materialising sampling_locations / attention_weights).
@@ -142,44 +142,63 @@ def ms_deform_attn_forward_fused(value, spatial_shapes, proj, reference_points, 
     out = torch.empty((N, S, M * C), dtype=value.dtype, device=value.device)
     _keep, host_ptr = _shapes_on_host(spatial_shapes)
     _require(host_ptr is not None, "the fused gather needs the level shapes on the host (locality_hint)")
-    rc = _native.launch(_native.lib.transoar_msda3d_forward_fused, value,
-                        value.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), reference_points.size(0) * S,
-                        out.data_ptr(), N, S, M, C, L, P, _DT[value.dtype], host_ptr, ok=() if strict else (-2,))
-    return None if rc else out          # -2, TRANSOAR_ERR_DIM: not a form the fused kernel covers
+    _native.launch(_native.lib.transoar_msda3d_forward_fused, value,
+                   value.data_ptr(), proj.data_ptr(), reference_points.data_ptr(), reference_points.size(0) * S,
+                   out.data_ptr(), N, S, M, C, L, P, _DT[value.dtype], host_ptr)
+    return out          # a form the kernel does not cover raises (TRANSOAR_ERR_DIM): ask plan() first
+
+
+PLAN_FIELDS = ("fwd", "bwd_query", "bwd_value", "coarse_first")          # TRANSOAR_PLAN_* of the header
+FWD_PCM, FWD_Q16 = 4, 5                                                  # TRANSOAR_FWD_PCM / _Q16: the point-column gathers
+
+
+def plan(value, spatial_shapes, Lq, P, loc_dtype, grad_proj=False, call_flags=None):
+    """-> (status, {field: kernel code}) of transoar_msda3d_plan: the kernels the forward and the backward (grad_proj: the
+    backward_proj entry) launch for this form and these flags (default: the module's).  Host arithmetic only.  status: 0,
+    ERR_MODE (the backward refuses the form) or an argument error, after which every field is 0."""
+    N, S, M, C = value.shape
+    _keep, host_ptr = _shapes_on_host(spatial_shapes)
+    out = (ctypes.c_int * len(PLAN_FIELDS))()
+    rc = _native.lib.transoar_msda3d_plan(N, S, M, C, spatial_shapes.size(0), Lq, P, _DT[value.dtype], _DT[loc_dtype],
+                                          host_ptr, flags if call_flags is None else call_flags, int(grad_proj), out)
+    return rc, dict(zip(PLAN_FIELDS, out))
+
+
+def _backward_dims(tensors, im2col_step):
+    """The input checks of both backward entries; tensors = (value, shapes, starts, loc, attn, grad_output)."""
+    _check_inputs(list(zip(("value", "spatial_shapes", "level_start_index", "sampling_loc", "attn_weight", "grad_output"), tensors)))
+    N, S, M, C, L, Lq, P = dims = _dims(*tensors[:5], im2col_step)
+    _require(tuple(tensors[5].shape) == (N, Lq, M * C) and tensors[5].dtype == tensors[0].dtype,
+             "grad_output must be (N, Lq, M*C) with value's dtype")
+    return dims
+
+
+def _backward(fn, tensors, grads, dims, call_flags):
+    """The launch of both backward entries: the workspace for `call_flags`, then ONE call of fn(*tensors, *grads, ...)."""
+    value, spatial_shapes, sampling_loc = tensors[0], tensors[1], tensors[3]
+    dims = (*dims, _DT[value.dtype], _DT[sampling_loc.dtype])
+    _keep, host_ptr = _shapes_on_host(spatial_shapes)
+    ws_bytes = _native.lib.transoar_msda3d_backward_workspace_bytes(*dims, call_flags)
+    workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=value.device)
+    _native.launch(fn, value, *[t.data_ptr() for t in tensors], *[g.data_ptr() for g in grads],
+                   workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags)
+    return grads
 
 
 def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                             grad_output, im2col_step):
     """-> [grad_value, grad_sampling_loc, grad_attn_weight]; replaces
     ops/src/ms_deform_attn.h:41-61."""
-    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes),
-                   ("level_start_index", level_start_index), ("sampling_loc", sampling_loc),
-                   ("attn_weight", attn_weight), ("grad_output", grad_output)])
-    N, S, M, C, L, Lq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc,
-                                 attn_weight, im2col_step)
-    _require(tuple(grad_output.shape) == (N, Lq, M * C) and grad_output.dtype == value.dtype,
-             "grad_output must be (N, Lq, M*C) with value's dtype")
+    dims = _backward_dims((value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output), im2col_step)
     loc_in_dtype, attn_in_dtype = sampling_loc.dtype, attn_weight.dtype
     sampling_loc, attn_weight = _coerce_loc(value, sampling_loc, attn_weight)
-    grad_value = torch.empty_like(value)
-    grad_loc = torch.empty_like(sampling_loc)
-    grad_attn = torch.empty_like(attn_weight)
-    dims = (N, S, M, C, L, Lq, P, _DT[value.dtype], _DT[sampling_loc.dtype])
-    _keep, host_ptr = _shapes_on_host(spatial_shapes)
-    torch_det = torch.are_deterministic_algorithms_enabled()
-
-    def run(call_flags, ok=()):
-        ws_bytes = _native.lib.transoar_msda3d_backward_workspace_bytes(*dims, call_flags)
-        workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=value.device)
-        return _native.launch(_native.lib.transoar_msda3d_backward, value,
-                              value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                              sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(),
-                              grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
-                              workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags, ok=ok)
-
+    call_flags = flags
     strict = deterministic or bool(flags & DETERMINISTIC)          # the switch itself: an uncovered form raises
-    if strict or torch_det:
-        if run(flags | DETERMINISTIC, ok=() if strict else (ERR_MODE,)) == ERR_MODE:
+    if strict or torch.are_deterministic_algorithms_enabled():
+        call_flags = flags | DETERMINISTIC
+        if plan(value, spatial_shapes, dims[5], dims[6], sampling_loc.dtype, call_flags=call_flags)[0] == ERR_MODE:
+            if strict:
+                _native.check(ERR_MODE, "transoar_msda3d_backward")
             if not torch.is_deterministic_algorithms_warn_only_enabled():
                 raise RuntimeError("ms_deform_attn_backward does not have a deterministic implementation for this form (16-bit "
                                    "storage, 64 channels, 4 points, <= 4 levels with queries = the pyramid's voxels are covered), "
@@ -187,33 +206,22 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
             import warnings
             warnings.warn("ms_deform_attn_backward: no deterministic implementation for this form; running the default "
                           "(atomic-order dependent) accumulation")
-            run(flags)
-    else:
-        run(flags)
-    return [grad_value, grad_loc.to(loc_in_dtype), grad_attn.to(attn_in_dtype)]
+            call_flags = flags
+    gv, gl, ga = _backward(_native.lib.transoar_msda3d_backward,
+                           (value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output),
+                           [torch.empty_like(value), torch.empty_like(sampling_loc), torch.empty_like(attn_weight)], dims, call_flags)
+    return [gv, gl.to(loc_in_dtype), ga.to(attn_in_dtype)]
 
 
 def ms_deform_attn_backward_proj(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
     """-> [grad_value, grad_proj] or None: the backward with the sampling head's backward folded into the query kernel
     (transoar_msda3d_backward_proj): grad_proj (N, Lq, 4*M*L*P) bf16 is the gradient of the stacked [sampling_offsets |
-    attention_weights] projection.  None when the form is not covered (TRANSOAR_ERR_MODE): the caller then runs
-    ms_deform_attn_backward and the head's own backward kernel."""
-    _check_inputs([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
-                   ("sampling_loc", sampling_loc), ("attn_weight", attn_weight), ("grad_output", grad_output)])
-    N, S, M, C, L, Lq, P = _dims(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)
-    _require(tuple(grad_output.shape) == (N, Lq, M * C) and grad_output.dtype == value.dtype,
-             "grad_output must be (N, Lq, M*C) with value's dtype")
-    if sampling_loc.dtype != torch.float32 or attn_weight.dtype != torch.float32 or value.dtype not in (torch.bfloat16, torch.float16):
-        return None
+    attention_weights] projection.  None, without a launch, when the plan says the form is not covered: the caller then
+    runs ms_deform_attn_backward and the head's own backward kernel."""
+    tensors = (value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output)
+    N, S, M, C, L, Lq, P = dims = _backward_dims(tensors, im2col_step)
     call_flags = flags | (DETERMINISTIC if (deterministic or torch.are_deterministic_algorithms_enabled()) else 0)
-    grad_value = torch.empty_like(value)
-    grad_proj = torch.empty((N, Lq, 4 * M * L * P), dtype=torch.bfloat16, device=value.device)
-    dims = (N, S, M, C, L, Lq, P, _DT[value.dtype], _DT[sampling_loc.dtype])
-    _keep, host_ptr = _shapes_on_host(spatial_shapes)
-    ws_bytes = _native.lib.transoar_msda3d_backward_workspace_bytes(*dims, call_flags)
-    workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=value.device)
-    rc = _native.launch(_native.lib.transoar_msda3d_backward_proj, value,
-                        value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                        attn_weight.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(), grad_proj.data_ptr(),
-                        workspace.data_ptr(), ws_bytes, *dims, host_ptr, call_flags, ok=(ERR_MODE,))
-    return None if rc else [grad_value, grad_proj]
+    if attn_weight.dtype != sampling_loc.dtype or plan(value, spatial_shapes, Lq, P, sampling_loc.dtype, True, call_flags)[0] != 0:
+        return None
+    grads = [torch.empty_like(value), torch.empty((N, Lq, 4 * M * L * P), dtype=torch.bfloat16, device=value.device)]
+    return _backward(_native.lib.transoar_msda3d_backward_proj, tensors, grads, dims, call_flags)
