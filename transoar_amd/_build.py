@@ -33,6 +33,7 @@ LIBS = {
     "libtransoar_criterion.so": ["criterion.hip"],
     "libtransoar_segproxy.so": ["seg_proxy.hip"],
     "libtransoar_boxtargets.so": ["box_targets.hip"],
+    "libtransoar_deteval.so": ["det_eval.hip"],
 }
 
 
