@@ -34,6 +34,7 @@ LIBS = {
     "libtransoar_segproxy.so": ["seg_proxy.hip"],
     "libtransoar_boxtargets.so": ["box_targets.hip"],
     "libtransoar_deteval.so": ["det_eval.hip"],
+    "libtransoar_augment.so": ["augment.hip"],
 }
 
 

@@ -1,0 +1,365 @@
+"""Batch augmentation on the device (include/transoar_augment.h, csrc/augment.hip): what the reference does for every batch on host
+workers -- TransoarDataset.__getitem__ -> get_transforms('train') of transoar/data/transforms.py:76-165, a MONAI chain that resamples
+each volume several times in a row -- as ONE launch per batch: intensity range scaling, one trilinear resample of the volume
+(nearest for its label map) through a per-sample affine map, and an intensity gain / offset.
+
+Built: ScaleIntensityRanged, RandRotated, RandZoomd, RandAffined (translate), the three RandFlipd, RandSpatialCropd,
+RandScaleIntensityd and RandShiftIntensityd -- the steps the two shipped YAMLs switch on (and the flips, which are sign changes in
+the same matrix).  NOT implemented: p_gaussian_noise, p_gaussian_smooth, p_adjust_contrast and p_shear above 0 raise a ValueError
+that names the key (all four are 0 in both YAMLs).
+
+Two deliberate differences from the reference:
+  * the spatial steps are composed into one affine map per sample and the volume is interpolated ONCE, trilinear; the reference
+    interpolates after every step and zooms in `area` mode;
+  * the parameters are drawn by this project's own seeded generator (a CPU torch.Generator), not MONAI's random stream.
+MONAI's Euler convention cannot be checked without MONAI; with the symmetric angle ranges of the YAMLs the distribution of the
+maps does not depend on it.
+
+The table (N, 16) fp32 and the operation are specified in include/transoar_augment.h.  `augment_torch` is that specification in
+batched torch with explicit index arithmetic (no grid_sample): the path for CPU tensors, for inputs the kernel does not take and
+for TRANSOAR_AUGMENT_HIP=0, and with dtype=torch.float64 the reference of the tests.  a_min and a_max are rounded to fp32 first
+in every path: the C ABI takes them as floats.
+"""
+import math
+import os
+
+import torch
+
+from . import _native
+
+lib = _native.bind("augment", abi=1)
+ENABLED = os.environ.get("TRANSOAR_AUGMENT_HIP", "1") != "0"
+PARAMS = 16
+MAX_COORD = float(2 ** 24)
+_LABEL_DT = {torch.uint8: 16, torch.int16: 17, torch.int32: 18, torch.int64: 19}
+UNSUPPORTED = ("p_gaussian_noise", "p_gaussian_smooth", "p_adjust_contrast", "p_shear")
+
+
+def _volume(t, what):
+    """(N, 1, D, H, W) or (N, D, H, W) -> (N, D, H, W)"""
+    if not torch.is_tensor(t) or t.dim() not in (4, 5) or (t.dim() == 5 and t.shape[1] != 1):
+        raise ValueError("%s: a tensor of shape (N, 1, D, H, W) or (N, D, H, W), got %s"
+                         % (what, str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__))
+    return t[:, 0] if t.dim() == 5 else t
+
+
+def _f32(x):
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _check_shapes(img, lab, params, out_shape):
+    n = img.shape[0]
+    out_shape = tuple(int(s) for s in out_shape)
+    if len(out_shape) != 3 or any(o < 1 or o > s for o, s in zip(out_shape, img.shape[1:])):
+        raise ValueError("out_shape %s: three extents, each between 1 and the input's %s" % (out_shape, tuple(img.shape[1:])))
+    if lab is not None and lab.shape != img.shape:
+        raise ValueError("labels of shape %s for an image of shape %s" % (tuple(lab.shape), tuple(img.shape)))
+    if not torch.is_tensor(params) or params.shape != (n, PARAMS):
+        raise ValueError("params: a tensor of shape (%d, %d)" % (n, PARAMS))
+    return out_shape
+
+
+def check_table(params):
+    """Refuse a table the kernel would treat as 'everything outside': an entry of [M | t] that is not finite or beyond +-2^24,
+    or a gain / offset that is not finite.  Host tables only (a device table is not read back)."""
+    p = params.detach().to(torch.float64)
+    if p.dim() != 2 or p.shape[1] != PARAMS:
+        raise ValueError("params: a table of shape (N, %d), got %s" % (PARAMS, tuple(p.shape)))
+    if not bool(torch.isfinite(p).all()) or float(p[:, :12].abs().max()) > MAX_COORD:
+        raise ValueError("params: every entry must be finite and the map's entries within +-2^24")
+    return params
+
+
+def usable(image, labels=None):
+    """Can the kernel take these inputs?"""
+    ok = (ENABLED and torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.dim() in (4, 5)
+          and image.numel() > 0 and image.shape[0] <= 65535)
+    if ok and labels is not None:
+        ok = torch.is_tensor(labels) and labels.is_cuda and labels.dtype in _LABEL_DT and labels.device == image.device
+    return bool(ok)
+
+
+def augment_into(image, labels, params, image_out, labels_out, a_min, a_max):
+    """The kernel on the current stream: image (N, [1,] Di, Hi, Wi) fp32, labels the same shape or None, params a DEVICE table
+    (N, 16) fp32 -> image_out (N, [1,] Do, Ho, Wo) fp32 and labels_out in place.  Capturable; nothing is read back."""
+    img, out = _volume(image, "image"), _volume(image_out, "image_out")
+    lab = None if labels is None else _volume(labels, "labels")
+    lout = None if labels_out is None else _volume(labels_out, "labels_out")
+    _check_shapes(img, lab, params, out.shape[1:])
+    assert usable(img, lab), "augment_into: fp32 CUDA image (and uint8 / int16 / int32 / int64 CUDA labels)"
+    assert img.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == img.shape[0]
+    assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous()
+    assert (lab is None) == (lout is None)
+    if lab is not None:
+        assert lab.is_contiguous() and lout.is_contiguous() and lout.dtype == lab.dtype and lout.shape == out.shape
+    n, di, hi, wi = img.shape
+    _native.launch(lib.transoar_augment_forward, img, img.data_ptr(), _native.ptr(lab), _LABEL_DT[lab.dtype] if lab is not None else 0,
+                   n, di, hi, wi, out.shape[1], out.shape[2], out.shape[3], params.data_ptr(), float(a_min), float(a_max),
+                   out.data_ptr(), _native.ptr(lout))
+
+
+def augment(image, labels, params, out_shape, a_min, a_max, out=None):
+    """-> (image (N, [1,] Do, Ho, Wo) fp32, labels or None), in the rank of the inputs.  params: the table (N, 16) fp32; a HOST
+    table is checked (check_table) and uploaded, a device table is taken as it is.  out=(image_out, labels_out) writes in place.
+    CUDA inputs go through the kernel, anything else (and TRANSOAR_AUGMENT_HIP=0) through augment_torch."""
+    img = _volume(image, "image")
+    lab = None if labels is None else _volume(labels, "labels")
+    out_shape = _check_shapes(img, lab, params, out_shape)
+    if not params.is_cuda:
+        check_table(params)
+    if not usable(img, lab):
+        got = augment_torch(image, labels, params.to(img.device), out_shape, a_min, a_max)
+        if out is not None:
+            out[0].copy_(got[0].view_as(out[0]))
+            if lab is not None:
+                out[1].copy_(got[1].view_as(out[1]))
+            return out[0], (out[1] if lab is not None else None)
+        return got
+    lead = image.shape[:image.dim() - 3]
+    if out is None:
+        out = (torch.empty(*lead, *out_shape, dtype=torch.float32, device=img.device),
+               None if lab is None else torch.empty(*labels.shape[:labels.dim() - 3], *out_shape, dtype=lab.dtype, device=img.device))
+    table = params.to(device=img.device, dtype=torch.float32, non_blocking=True).contiguous()
+    augment_into(image.contiguous(), None if lab is None else labels.contiguous(), table, out[0], None if lab is None else out[1],
+                 a_min, a_max)
+    return out[0], (out[1] if lab is not None else None)
+
+
+def augment_torch(image, labels, params, out_shape, a_min, a_max, dtype=torch.float32):
+    """The specification of include/transoar_augment.h in batched torch on the inputs' device: explicit index arithmetic, every
+    corner gathered from a clamped address and selected by torch.where.  The source coordinates, their floor and fraction are
+    always fp64 (as in the kernel); the weights, the range scaling, the sum and gain / offset are in `dtype`.  With torch.float64
+    it is the reference of the tests.  -> (image in `dtype`, labels or None), in the rank of the inputs."""
+    img = _volume(image, "image")
+    lab = None if labels is None else _volume(labels, "labels")
+    do, ho, wo = _check_shapes(img, lab, params, out_shape)
+    n, di, hi, wi = img.shape
+    dev = img.device
+    p32 = params.to(device=dev, dtype=torch.float32)
+    p64 = p32.to(torch.float64)
+    lo = torch.tensor(_f32(a_min), dtype=dtype, device=dev)
+    rng = (torch.tensor(_f32(a_max), dtype=torch.float32, device=dev) - lo.to(torch.float32)).to(dtype)       # the kernel's fp32 range
+    v = ((img.to(dtype) - lo) / rng).clamp(0, 1).reshape(n, -1)
+    grid = [torch.arange(s, dtype=torch.float64, device=dev).view(shape) for s, shape in
+            ((do, (1, -1, 1, 1)), (ho, (1, 1, -1, 1)), (wo, (1, 1, 1, -1)))]
+    col = lambda k: p64[:, k].view(n, 1, 1, 1)
+    s = [col(4 * a + 2) * grid[2] + (col(4 * a + 1) * grid[1] + (col(4 * a) * grid[0] + col(4 * a + 3))) for a in range(3)]
+    usable_ = torch.ones(n, do, ho, wo, dtype=torch.bool, device=dev)
+    for sa in s:
+        usable_ = usable_ & (sa.abs() <= MAX_COORD)            # false for a NaN too
+    sizes = (di, hi, wi)
+    zero, zero64 = torch.zeros((), dtype=dtype, device=dev), torch.zeros((), dtype=torch.float64, device=dev)
+
+    def linear(idx):
+        return ((idx[0].clamp(0, di - 1) * hi + idx[1].clamp(0, hi - 1)) * wi + idx[2].clamp(0, wi - 1)).reshape(n, -1)
+
+    base, frac = [], []
+    for sa in s:
+        f = torch.where(usable_, sa.floor(), zero64)
+        base.append(f.to(torch.int64))
+        frac.append(torch.where(usable_, sa - f, zero64).to(dtype))
+    acc = torch.zeros(n, do, ho, wo, dtype=dtype, device=dev)
+    for c in range(8):
+        k = (c >> 2, (c >> 1) & 1, c & 1)
+        idx = [base[a] + k[a] for a in range(3)]
+        inside = usable_
+        for a in range(3):
+            inside = inside & (idx[a] >= 0) & (idx[a] < sizes[a])
+        w = [frac[a] if k[a] else 1 - frac[a] for a in range(3)]
+        wgt = (w[0] * w[1]) * w[2]
+        val = v.gather(1, linear(idx)).view(n, do, ho, wo)
+        acc = acc + torch.where(inside, wgt * val, zero)
+    out = acc * p32[:, 12].to(dtype).view(n, 1, 1, 1)
+    out = out + p32[:, 13].to(dtype).view(n, 1, 1, 1)
+    lead = image.shape[:image.dim() - 3]
+    out = out.view(*lead, do, ho, wo)
+    if lab is None:
+        return out, None
+    idx = [torch.where(usable_, (sa + 0.5).floor(), -torch.ones((), dtype=torch.float64, device=dev)).to(torch.int64) for sa in s]
+    inside = usable_
+    for a in range(3):
+        inside = inside & (idx[a] >= 0) & (idx[a] < sizes[a])
+    got = lab.reshape(n, -1).gather(1, linear(idx)).view(n, do, ho, wo)
+    got = torch.where(inside, got, torch.zeros((), dtype=lab.dtype, device=dev))
+    return out, got.view(*labels.shape[:labels.dim() - 3], do, ho, wo)
+
+
+# ---- the table of a chain ------------------------------------------------------------------------------------------------------
+def _cos_sin_deg(a):
+    """cos and sin of an angle in degrees, exact (0, +-1) at the multiples of 90."""
+    q = math.fmod(float(a), 360.0)
+    if q % 90.0 == 0.0:
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q // 90) % 4]
+    r = math.radians(q)
+    return math.cos(r), math.sin(r)
+
+
+def _rotation(angles):
+    """Rx Ry Rz on (D, H, W): Rx turns the (H, W) plane, Ry the (D, W) plane, Rz the (D, H) plane; angles in degrees; fp64."""
+    (cx, sx), (cy, sy), (cz, sz) = (_cos_sin_deg(a) for a in angles)
+    rx = torch.tensor([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], dtype=torch.float64)
+    ry = torch.tensor([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], dtype=torch.float64)
+    rz = torch.tensor([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], dtype=torch.float64)
+    return rx @ ry @ rz
+
+
+def _per_sample(x, n, width, default, what):
+    if x is None:
+        x = default
+    t = torch.as_tensor(x, dtype=torch.float64)
+    t = t.expand(n, width) if width else t.expand(n)
+    if t.shape != ((n, width) if width else (n,)):
+        raise ValueError("%s: one value per sample%s" % (what, " and axis" if width else ""))
+    return t
+
+
+def compose_params(n, in_shape, angles=None, zoom=None, translate=None, flips=None, crop=None, gain=None, offset=None):
+    """The table (n, 16) fp32 (a CPU tensor) of the chain  rotate -> zoom -> translate -> flip -> crop  and of  v * gain + offset,
+    computed in fp64 and rounded once.  Per sample (a value without a batch axis is shared): angles (3) in DEGREES about (D, H, W),
+    zoom (1), translate (3) in voxels, flips (3) booleans, crop (3) the integer offset of the output window, gain, offset.
+
+    With S = in_shape, c = (S - 1) / 2, R = Rx Ry Rz, F = diag(-1 where flipped), f = S - 1 where flipped else 0: the output ->
+    source map is the product of the steps' maps in reverse chain order,
+        src = c + (R / z) (F (o + crop) + f - tr - c),     i.e.  M = (R / z) F,  t = c + (R / z) (F crop + f - tr - c)."""
+    size = torch.tensor([float(s) for s in in_shape], dtype=torch.float64)
+    if size.shape != (3,):
+        raise ValueError("in_shape: three extents")
+    c = (size - 1) / 2
+    angles = _per_sample(angles, n, 3, 0.0, "angles")
+    zoom = _per_sample(zoom, n, 0, 1.0, "zoom")
+    translate = _per_sample(translate, n, 3, 0.0, "translate")
+    flips = _per_sample(None if flips is None else torch.as_tensor(flips).to(torch.float64), n, 3, 0.0, "flips")
+    crop = _per_sample(crop, n, 3, 0.0, "crop")
+    gain = _per_sample(gain, n, 0, 1.0, "gain")
+    offset = _per_sample(offset, n, 0, 0.0, "offset")
+    if bool((zoom <= 0).any()):
+        raise ValueError("zoom must be positive")
+    table = torch.zeros(n, PARAMS, dtype=torch.float64)
+    for i in range(n):
+        a = _rotation(angles[i].tolist()) / zoom[i]
+        sign = 1 - 2 * flips[i]
+        m = a * sign[None, :]
+        t = c + a @ (sign * crop[i] + flips[i] * (size - 1) - translate[i] - c)
+        table[i, :12] = torch.cat((m, t[:, None]), 1).reshape(12)
+        table[i, 12], table[i, 13] = gain[i], offset[i]
+    return table.to(torch.float32)
+
+
+# ---- the reference's configuration -> tables -------------------------------------------------------------------------------------
+class BatchAugment:
+    """The reference's per-batch transform chain for `split` ('train', 'val' or 'test'), read from the reference's keys:
+    config['augmentation'], config['foreground_voxel_statistics'] (percentile_00_5 / percentile_99_5 -> a_min / a_max),
+    config['shape_statistics']['median'] (the translation range and, without a patch_size, the output shape).
+
+    aug = BatchAugment(config, 'train', seed)
+    x, lab = aug(image, labels)                       # (N, 1, Do, Ho, Wo) fp32 and labels: what TrainStep and Validator.add take
+    aug(image, labels, out=step.static_inputs())      # straight into the captured step's buffers
+
+    'val' and 'test' scale the range and crop only: centred with deterministic=True, at a random position otherwise (as the
+    reference's RandSpatialCropd).  On CUDA inputs a call draws on the host, copies the table from a pinned slot without blocking
+    and launches: no host synchronisation per batch.  The pinned slots form a ring with one event each (recorded after the launch
+    that reads the slot's table), waited on only when the ring wraps, so a draw never overwrites memory an earlier copy or launch
+    may still be reading."""
+
+    SLOTS = 4
+
+    def __init__(self, config, split="train", seed=0, deterministic=False):
+        if split not in ("train", "val", "test"):
+            raise ValueError("Please use 'test', 'val', or 'train' as split arg.")
+        a = config["augmentation"]
+        if split == "train":
+            for key in UNSUPPORTED:
+                if float(a.get(key, 0) or 0) > 0:
+                    raise ValueError("augmentation.%s = %r: not implemented on the device (only 0 is supported)" % (key, a[key]))
+        self.split, self.deterministic, self.aug = split, bool(deterministic), a
+        stats = config["foreground_voxel_statistics"]
+        self.a_min, self.a_max = _f32(stats["percentile_00_5"]), _f32(stats["percentile_99_5"])
+        if not self.a_max > self.a_min:
+            raise ValueError("foreground_voxel_statistics: percentile_99_5 must exceed percentile_00_5")
+        median = [float(s) for s in config["shape_statistics"]["median"]]
+        patch = a.get("patch_size")
+        self.out_shape = tuple(int(round(s)) for s in (median if patch is None else patch))
+        self.translate_range = [m * float(a.get("translate_precentage", 0)) / 100 for m in median]
+        self.generator = torch.Generator().manual_seed(int(seed))
+        self._slots = {}
+
+    def _uniform(self, n, lo, hi, width=None):
+        shape = (n,) if width is None else (n, width)
+        return lo + (hi - lo) * torch.rand(shape, dtype=torch.float64, generator=self.generator)
+
+    def _applied(self, n, key):
+        """Which samples take the step, with the probability of config['augmentation'][key]."""
+        p = float(self.aug.get(key, 0) or 0)
+        return torch.rand(n, dtype=torch.float64, generator=self.generator) < p
+
+    def sample(self, n, in_shape=None):
+        """The drawn steps of n samples, as compose_params takes them (identity values where a step is not applied)."""
+        in_shape = self.out_shape if in_shape is None else tuple(int(s) for s in in_shape)
+        if any(o > s for o, s in zip(self.out_shape, in_shape)):
+            raise ValueError("the patch %s does not fit the stored volume %s" % (self.out_shape, in_shape))
+        room = torch.tensor([s - o for s, o in zip(in_shape, self.out_shape)], dtype=torch.float64)
+        steps = dict(angles=torch.zeros(n, 3, dtype=torch.float64), zoom=torch.ones(n, dtype=torch.float64),
+                     translate=torch.zeros(n, 3, dtype=torch.float64), flips=torch.zeros(n, 3, dtype=torch.bool),
+                     gain=torch.ones(n, dtype=torch.float64), offset=torch.zeros(n, dtype=torch.float64))
+        if self.split == "train":
+            a = self.aug
+            lo, hi = (float(x) for x in a.get("rotation", (0, 0)))
+            on = self._applied(n, "p_rotate")
+            steps["angles"] = torch.where(on[:, None], self._uniform(n, lo, hi, 3), steps["angles"])
+            on = self._applied(n, "p_zoom")
+            steps["zoom"] = torch.where(on, self._uniform(n, float(a.get("min_zoom", 1)), float(a.get("max_zoom", 1))), steps["zoom"])
+            on = self._applied(n, "p_translate")
+            reach = torch.tensor(self.translate_range, dtype=torch.float64)
+            steps["translate"] = torch.where(on[:, None], (2 * self._uniform(n, 0.0, 1.0, 3) - 1) * reach, steps["translate"])
+            axes = [int(x) for x in a.get("flip_axis", (0, 1, 2))]
+            for axis in axes:                                  # one RandFlipd per listed axis, each with p_flip
+                steps["flips"][:, axis] = self._applied(n, "p_flip")
+            f = float(a.get("intensity_scale_factors", 0))
+            on = self._applied(n, "p_intensity_scale")
+            steps["gain"] = torch.where(on, 1 + self._uniform(n, -f, f), steps["gain"])
+            o = float(a.get("intensity_shift_offsets", 0))
+            on = self._applied(n, "p_intensity_shift")
+            steps["offset"] = torch.where(on, self._uniform(n, -o, o), steps["offset"])
+        if self.split != "train" and self.deterministic:
+            steps["crop"] = (room // 2).expand(n, 3).clone()
+        else:
+            steps["crop"] = torch.floor(self._uniform(n, 0.0, 1.0, 3) * (room + 1)).clamp(max=room)
+        return steps
+
+    def draw(self, n, in_shape=None):
+        """-> the table (n, 16) fp32 of n freshly drawn samples (a CPU tensor)."""
+        in_shape = self.out_shape if in_shape is None else tuple(int(s) for s in in_shape)
+        return check_table(compose_params(n, in_shape, **self.sample(n, in_shape)))
+
+    def _upload(self, table, device):
+        """-> (the table on `device`, copied from a pinned slot of the ring without blocking; the slot's event, to be recorded
+        after the launch that reads the table: it then covers both the copy out of the pinned slot and the kernel's reads)."""
+        key = (device, table.shape[0])
+        ring = self._slots.get(key)
+        if ring is None:
+            ring = self._slots[key] = dict(next=0, slots=[
+                dict(pinned=torch.empty(table.shape, dtype=torch.float32).pin_memory(),
+                     device=torch.empty(table.shape, dtype=torch.float32, device=device), event=None)
+                for _ in range(self.SLOTS)])
+        slot = ring["slots"][ring["next"] % self.SLOTS]
+        ring["next"] += 1
+        if slot["event"] is None:
+            slot["event"] = torch.cuda.Event()
+        else:
+            slot["event"].synchronize()          # the copy and the launch that read this slot SLOTS calls ago have finished
+        slot["pinned"].copy_(table)
+        slot["device"].copy_(slot["pinned"], non_blocking=True)
+        return slot["device"], slot["event"]
+
+    def __call__(self, image, labels=None, out=None):
+        img = _volume(image, "image")
+        n = img.shape[0]
+        lab = None if labels is None else _volume(labels, "labels")
+        table, event = self.draw(n, img.shape[1:]), None
+        if usable(img, lab):
+            with torch.cuda.device(img.device):
+                table, event = self._upload(table, img.device)
+        got = augment(img[:, None], None if lab is None else lab[:, None], table, self.out_shape, self.a_min, self.a_max, out=out)
+        if event is not None:
+            event.record(torch.cuda.current_stream(img.device))
+        return got

@@ -442,6 +442,15 @@ class TrainStep:
             self._replay_done.record()
         return self._static_total, self._static_losses
 
+    def static_inputs(self):
+        """The captured step's own input buffers (data, seg_targets), or None without a captured graph (seg_targets is None for
+        a step captured without a label volume).  A producer that writes them in place -- BatchAugment(...)(raw, raw_labels,
+        out=step.static_inputs()) -- and then calls step(data, targets, seg_targets) with these very tensors replays with no
+        copy: _replay copies an input only when its address differs."""
+        if self._graph is None:
+            return None
+        return self._static_x, self._static_seg
+
     def drop_graph(self):
         """Back to the eager step (with its overlapped gradient exchange)."""
         self._graph = None
