@@ -35,6 +35,7 @@ LIBS = {
     "libtransoar_boxtargets.so": ["box_targets.hip"],
     "libtransoar_deteval.so": ["det_eval.hip"],
     "libtransoar_augment.so": ["augment.hip"],
+    "libtransoar_resize.so": ["resize.hip"],
 }
 
 

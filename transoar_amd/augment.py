@@ -246,6 +246,28 @@ def compose_params(n, in_shape, angles=None, zoom=None, translate=None, flips=No
 
 
 # ---- the reference's configuration -> tables -------------------------------------------------------------------------------------
+def upload_through_ring(rings, count, table, device):
+    """A host table of any dtype -> (the table on `device`, copied from a pinned slot without blocking; the slot's event, to be
+    recorded after the launch that reads the table).  `rings` is the caller's dict of rings, one per (device, rows) with `count`
+    slots each; a slot is reused only after its event has completed (waited on when the ring wraps)."""
+    key = (device, table.shape[0])
+    ring = rings.get(key)
+    if ring is None:
+        ring = rings[key] = dict(next=0, slots=[
+            dict(pinned=torch.empty(table.shape, dtype=table.dtype).pin_memory(),
+                 device=torch.empty(table.shape, dtype=table.dtype, device=device), event=None)
+            for _ in range(count)])
+    slot = ring["slots"][ring["next"] % count]
+    ring["next"] += 1
+    if slot["event"] is None:
+        slot["event"] = torch.cuda.Event()
+    else:
+        slot["event"].synchronize()          # the copy and the launch that read this slot `count` calls ago have finished
+    slot["pinned"].copy_(table)
+    slot["device"].copy_(slot["pinned"], non_blocking=True)
+    return slot["device"], slot["event"]
+
+
 class BatchAugment:
     """The reference's per-batch transform chain for `split` ('train', 'val' or 'test'), read from the reference's keys:
     config['augmentation'], config['foreground_voxel_statistics'] (percentile_00_5 / percentile_99_5 -> a_min / a_max),
@@ -256,7 +278,8 @@ class BatchAugment:
     aug(image, labels, out=step.static_inputs())      # straight into the captured step's buffers
 
     'val' and 'test' scale the range and crop only: centred with deterministic=True, at a random position otherwise (as the
-    reference's RandSpatialCropd).  On CUDA inputs a call draws on the host, copies the table from a pinned slot without blocking
+    reference's RandSpatialCropd).  Cases whose stored shape is not the median go through transoar_amd.resize.TestSplit, which
+    resizes them first as the reference's 'test' chain does.  On CUDA inputs a call draws on the host, copies the table from a pinned slot without blocking
     and launches: no host synchronisation per batch.  The pinned slots form a ring with one event each (recorded after the launch
     that reads the slot's table), waited on only when the ring wraps, so a draw never overwrites memory an earlier copy or launch
     may still be reading."""
@@ -334,22 +357,7 @@ class BatchAugment:
     def _upload(self, table, device):
         """-> (the table on `device`, copied from a pinned slot of the ring without blocking; the slot's event, to be recorded
         after the launch that reads the table: it then covers both the copy out of the pinned slot and the kernel's reads)."""
-        key = (device, table.shape[0])
-        ring = self._slots.get(key)
-        if ring is None:
-            ring = self._slots[key] = dict(next=0, slots=[
-                dict(pinned=torch.empty(table.shape, dtype=torch.float32).pin_memory(),
-                     device=torch.empty(table.shape, dtype=torch.float32, device=device), event=None)
-                for _ in range(self.SLOTS)])
-        slot = ring["slots"][ring["next"] % self.SLOTS]
-        ring["next"] += 1
-        if slot["event"] is None:
-            slot["event"] = torch.cuda.Event()
-        else:
-            slot["event"].synchronize()          # the copy and the launch that read this slot SLOTS calls ago have finished
-        slot["pinned"].copy_(table)
-        slot["device"].copy_(slot["pinned"], non_blocking=True)
-        return slot["device"], slot["event"]
+        return upload_through_ring(self._slots, self.SLOTS, table, device)
 
     def __call__(self, image, labels=None, out=None):
         img = _volume(image, "image")
