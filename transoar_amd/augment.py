@@ -5,8 +5,13 @@ each volume several times in a row -- as ONE launch per batch: intensity range s
 
 Built: ScaleIntensityRanged, RandRotated, RandZoomd, RandAffined (translate), the three RandFlipd, RandSpatialCropd,
 RandScaleIntensityd and RandShiftIntensityd -- the steps the two shipped YAMLs switch on (and the flips, which are sign changes in
-the same matrix).  NOT implemented: p_gaussian_noise, p_gaussian_smooth, p_adjust_contrast and p_shear above 0 raise a ValueError
-that names the key (all four are 0 in both YAMLs).
+the same matrix).  The four steps both YAMLs switch off -- RandGaussianNoised, RandGaussianSmoothd, RandAdjustContrastd and the
+shear RandAffined -- are opt-in: BatchAugment(..., full_chain=True).  Without it p_gaussian_noise, p_gaussian_smooth,
+p_adjust_contrast and p_shear above 0 raise a ValueError that names the key.  Shear is one more factor of the affine map
+(compose_params(shear=...)); the other three are the intensity tail, a launch sequence of its own after the resample
+(transoar_augment_intensity: intensity_into, its table from compose_intensity, its specification in torch intensity_torch).
+The order of the six shear coefficients and their padding with zeros are MONAI's create_shear as remembered: MONAI is not
+installed, so neither can be checked here (with the YAMLs' symmetric ranges the distribution does not depend on the sign).
 
 Two deliberate differences from the reference:
   * the spatial steps are composed into one affine map per sample and the volume is interpolated ONCE, trilinear; the reference
@@ -32,7 +37,10 @@ ENABLED = os.environ.get("TRANSOAR_AUGMENT_HIP", "1") != "0"
 PARAMS = 16
 MAX_COORD = float(2 ** 24)
 _LABEL_DT = {torch.uint8: 16, torch.int16: 17, torch.int32: 18, torch.int64: 19}
-UNSUPPORTED = ("p_gaussian_noise", "p_gaussian_smooth", "p_adjust_contrast", "p_shear")
+UNSUPPORTED = ("p_gaussian_noise", "p_gaussian_smooth", "p_adjust_contrast", "p_shear")     # without full_chain=True
+TAIL_WORDS = 12
+NOISE, SMOOTH, CONTRAST = 1, 2, 4
+MAX_SIGMA = 4.0
 
 
 def _volume(t, what):
@@ -213,14 +221,19 @@ def _per_sample(x, n, width, default, what):
     return t
 
 
-def compose_params(n, in_shape, angles=None, zoom=None, translate=None, flips=None, crop=None, gain=None, offset=None):
-    """The table (n, 16) fp32 (a CPU tensor) of the chain  rotate -> zoom -> translate -> flip -> crop  and of  v * gain + offset,
-    computed in fp64 and rounded once.  Per sample (a value without a batch axis is shared): angles (3) in DEGREES about (D, H, W),
-    zoom (1), translate (3) in voxels, flips (3) booleans, crop (3) the integer offset of the output window, gain, offset.
+def compose_params(n, in_shape, angles=None, zoom=None, translate=None, flips=None, crop=None, gain=None, offset=None, shear=None):
+    """The table (n, 16) fp32 (a CPU tensor) of the chain  rotate -> zoom -> translate -> [shear ->] flip -> crop  and of
+    v * gain + offset, computed in fp64 and rounded once.  Per sample (a value without a batch axis is shared): angles (3) in
+    DEGREES about (D, H, W), zoom (1), translate (3) in voxels, flips (3) booleans, crop (3) the integer offset of the output
+    window, gain, offset, and shear (6) the coefficients (s01, s02, s10, s12, s20, s21) of Sh = I + those off-diagonal entries.
 
     With S = in_shape, c = (S - 1) / 2, R = Rx Ry Rz, F = diag(-1 where flipped), f = S - 1 where flipped else 0: the output ->
     source map is the product of the steps' maps in reverse chain order,
-        src = c + (R / z) (F (o + crop) + f - tr - c),     i.e.  M = (R / z) F,  t = c + (R / z) (F crop + f - tr - c)."""
+        src = c + (R / z) (F (o + crop) + f - tr - c),     i.e.  M = (R / z) F,  t = c + (R / z) (F crop + f - tr - c),
+    and with a shear
+        src = c + (R / z) (Sh (F (o + crop) + f - c) - tr),  i.e.  M = (R / z) Sh F,  t = c + (R / z) (Sh (F crop + f - c) - tr).
+    shear=None is the first form, bit for bit.  The order of the six coefficients is MONAI's create_shear as remembered; it
+    cannot be checked here (MONAI is not installed)."""
     size = torch.tensor([float(s) for s in in_shape], dtype=torch.float64)
     if size.shape != (3,):
         raise ValueError("in_shape: three extents")
@@ -232,17 +245,191 @@ def compose_params(n, in_shape, angles=None, zoom=None, translate=None, flips=No
     crop = _per_sample(crop, n, 3, 0.0, "crop")
     gain = _per_sample(gain, n, 0, 1.0, "gain")
     offset = _per_sample(offset, n, 0, 0.0, "offset")
+    if shear is not None:
+        shear = _per_sample(shear, n, 6, 0.0, "shear")
     if bool((zoom <= 0).any()):
         raise ValueError("zoom must be positive")
     table = torch.zeros(n, PARAMS, dtype=torch.float64)
     for i in range(n):
         a = _rotation(angles[i].tolist()) / zoom[i]
         sign = 1 - 2 * flips[i]
-        m = a * sign[None, :]
-        t = c + a @ (sign * crop[i] + flips[i] * (size - 1) - translate[i] - c)
+        if shear is None:
+            m = a * sign[None, :]
+            t = c + a @ (sign * crop[i] + flips[i] * (size - 1) - translate[i] - c)
+        else:
+            s01, s02, s10, s12, s20, s21 = shear[i].tolist()
+            sh = torch.tensor([[1, s01, s02], [s10, 1, s12], [s20, s21, 1]], dtype=torch.float64)
+            m = (a @ sh) * sign[None, :]
+            t = c + a @ (sh @ (sign * crop[i] + flips[i] * (size - 1) - c) - translate[i])
         table[i, :12] = torch.cat((m, t[:, None]), 1).reshape(12)
         table[i, 12], table[i, 13] = gain[i], offset[i]
     return table.to(torch.float32)
+
+
+# ---- the intensity tail: noise -> smooth -> gain -> offset -> contrast (include/transoar_augment.h) -------------------------------
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+_MASK32 = 0xFFFFFFFF
+
+
+def _mulhilo(m, x):
+    """(hi, lo) 32-bit words of m * x for a constant m < 2^32 and an int64 tensor x of values < 2^32, without leaving int64:
+    x is split into 16-bit halves, so every product stays below 2^48."""
+    p, q = m * (x & 0xFFFF), m * (x >> 16)
+    return (q + (p >> 16)) >> 16, (((q & 0xFFFF) << 16) + (p & _MASK32)) & _MASK32
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 in int64 arithmetic.  counter: four int64 tensors (or ints) of 32-bit words, key: two -> four int64 tensors."""
+    c = [torch.as_tensor(x, dtype=torch.int64) & _MASK32 for x in counter]
+    k = [torch.as_tensor(x, dtype=torch.int64) & _MASK32 for x in key]
+    for _ in range(10):
+        hi0, lo0 = _mulhilo(_PHILOX_M[0], c[0])
+        hi1, lo1 = _mulhilo(_PHILOX_M[1], c[2])
+        c = [hi1 ^ c[1] ^ k[0], lo1, hi0 ^ c[3] ^ k[1], lo0]
+        k = [(k[0] + _PHILOX_W[0]) & _MASK32, (k[1] + _PHILOX_W[1]) & _MASK32]
+    return c
+
+
+def philox_normals(count, k0, k1, dtype=torch.float64, device=None):
+    """The normals of the voxels 0 .. count - 1 of samples with the keys k0, k1 (int64 tensors (n,)) -> (n, count) in `dtype`:
+    voxel i takes word i & 3 of call i >> 2 (Box-Muller on the four words, see the header)."""
+    calls = (count + 3) // 4
+    j = torch.arange(calls, dtype=torch.int64, device=device)[None, :]
+    k0 = torch.as_tensor(k0, dtype=torch.int64, device=device).view(-1, 1)
+    k1 = torch.as_tensor(k1, dtype=torch.int64, device=device).view(-1, 1)
+    zero = torch.zeros_like(j)
+    r = philox4x32((j & _MASK32, j >> 32, zero, zero), (k0, k1))
+    z = []
+    for p in range(2):
+        u1 = (((r[2 * p] >> 9).to(torch.float32) + 0.5) * 2.0 ** -23).to(dtype)      # exact in fp32
+        u2 = ((r[2 * p + 1] >> 9).to(torch.float32) * 2.0 ** -23).to(dtype)
+        rad = torch.sqrt(-2 * torch.log(u1))
+        z += [rad * torch.cos(2 * math.pi * u2), rad * torch.sin(2 * math.pi * u2)]
+    return torch.stack(z, -1).reshape(k0.shape[0], 4 * calls)[:, :count]
+
+
+def smooth_tail(sigma):
+    """The radius of MONAI's GaussianFilter(truncated=4) for a sigma, int(max(4 sigma, 0.5) + 0.5), in fp32 as the kernel."""
+    s = torch.tensor(float(sigma), dtype=torch.float32)
+    return int(torch.clamp(4 * s, min=0.5) + 0.5)
+
+
+def smooth_weights(sigma, dtype=torch.float64, device=None):
+    """The normalised taps x = -tail .. tail of MONAI's GaussianFilter(approx='erf', truncated=4) for an fp32 sigma in (0, 4]."""
+    tail = smooth_tail(sigma)
+    x = torch.arange(-tail, tail + 1, dtype=dtype, device=device)
+    t = 0.70710678 / torch.tensor(_f32(sigma), dtype=dtype, device=device)
+    w = (0.5 * (torch.erf(t * (x + 0.5)) - torch.erf(t * (x - 0.5)))).clamp(min=0)
+    return w / w.sum()
+
+
+def _tail_table(table, n):
+    if not torch.is_tensor(table) or table.shape != (n, TAIL_WORDS) or table.dtype != torch.int32:
+        raise ValueError("table: an int32 tensor of shape (%d, %d) (compose_intensity)" % (n, TAIL_WORDS))
+    return table
+
+
+def compose_intensity(n, flags=0, noise_mean=0.0, noise_std=0.0, sigma=(1.0, 1.0, 1.0), gain=1.0, offset=0.0, gamma=1.0, keys=(0, 0)):
+    """The tail's table (n, 12) of 32-bit words, an int32 CPU tensor whose floating entries are fp32 bit patterns.  Per sample (a
+    value without a batch axis is shared): flags (NOISE | SMOOTH | CONTRAST), noise_mean, noise_std, sigma (3) about (D, H, W),
+    gain, offset, gamma, keys (2) of 32 bits each (given as non-negative integers)."""
+    f = torch.zeros(n, TAIL_WORDS, dtype=torch.float32)
+    f[:, 1] = _per_sample(noise_mean, n, 0, 0.0, "noise_mean")
+    f[:, 2] = _per_sample(noise_std, n, 0, 0.0, "noise_std")
+    f[:, 3:6] = _per_sample(sigma, n, 3, 1.0, "sigma")
+    f[:, 6] = _per_sample(gain, n, 0, 1.0, "gain")
+    f[:, 7] = _per_sample(offset, n, 0, 0.0, "offset")
+    f[:, 8] = _per_sample(gamma, n, 0, 1.0, "gamma")
+    table = f.view(torch.int32).clone()
+    words = torch.cat((torch.as_tensor(flags, dtype=torch.int64).expand(n)[:, None], torch.as_tensor(keys, dtype=torch.int64).expand(n, 2)), 1)
+    if bool(((words < 0) | (words > _MASK32)).any()):
+        raise ValueError("flags and keys: 32-bit words, 0 .. 2^32 - 1")
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)              # the same bits
+    table[:, 0], table[:, 9], table[:, 10] = words[:, 0], words[:, 1], words[:, 2]
+    return table
+
+
+def intensity_torch(image, table, dtype=torch.float32):
+    """The specification of transoar_augment_intensity in torch on the inputs' device (index arithmetic and F.conv3d only; Philox
+    in int64): image (N, [1,] D, H, W), table (N, 12) int32 -> the image in `dtype`, in the rank of the input.  Every flag of a
+    row counts (there is no `steps`).  The path for CPU tensors and TRANSOAR_AUGMENT_HIP=0; with torch.float64 the tests'
+    reference."""
+    import torch.nn.functional as F
+    img = _volume(image, "image")
+    n, d, h, w = img.shape
+    dev = img.device
+    words = _tail_table(table, n).to(dev)
+    f = words.view(torch.float32)
+    flags = words[:, 0].to(torch.int64) & 7
+    v = img.to(dtype)
+    # noise
+    on = ((flags & NOISE) != 0) & torch.isfinite(f[:, 1]) & torch.isfinite(f[:, 2])
+    if bool(on.any()):
+        z = philox_normals(d * h * w, words[:, 9].to(torch.int64) & _MASK32, words[:, 10].to(torch.int64) & _MASK32, dtype, dev)
+        mean = torch.where(on, f[:, 1], torch.zeros_like(f[:, 1])).to(dtype).view(n, 1)
+        std = torch.where(on, f[:, 2], torch.zeros_like(f[:, 2])).to(dtype).view(n, 1)
+        v = torch.where(on.view(n, 1, 1, 1), v + (mean + std * z).view(n, d, h, w), v)
+    # smoothing: a sample's three axes one after another, zero padding
+    sig = f[:, 3:6]
+    on = ((flags & SMOOTH) != 0) & ((sig > 0) & (sig <= MAX_SIGMA)).all(1)
+    if bool(on.any()):
+        rows = []
+        for i in range(n):
+            x = v[i][None, None]
+            if bool(on[i]):
+                for axis in range(3):
+                    wts = smooth_weights(float(sig[i, axis]), dtype, dev)
+                    shape, pad = [1, 1, 1, 1, 1], [0, 0, 0]
+                    shape[2 + axis], pad[axis] = wts.numel(), wts.numel() // 2
+                    x = F.conv3d(x, wts.view(shape), padding=pad)
+            rows.append(x[0, 0])
+        v = torch.stack(rows)
+    # gain and offset (two roundings)
+    gain = torch.where(torch.isfinite(f[:, 6]), f[:, 6], torch.ones_like(f[:, 6])).to(dtype).view(n, 1, 1, 1)
+    offset = torch.where(torch.isfinite(f[:, 7]), f[:, 7], torch.zeros_like(f[:, 7])).to(dtype).view(n, 1, 1, 1)
+    v = v * gain
+    v = v + offset
+    # contrast
+    on = ((flags & CONTRAST) != 0) & torch.isfinite(f[:, 8]) & (f[:, 8] > 0)
+    if bool(on.any()):
+        mn = v.reshape(n, -1).min(1).values.view(n, 1, 1, 1)
+        rng = v.reshape(n, -1).max(1).values.view(n, 1, 1, 1) - mn
+        gamma = torch.where(on, f[:, 8], torch.ones_like(f[:, 8])).to(dtype).view(n, 1, 1, 1)
+        y = ((v - mn) / (rng + 1e-7)) ** gamma * rng + mn
+        v = torch.where(on.view(n, 1, 1, 1), y, v)
+    return v.view(image.shape)
+
+
+def intensity_workspace(n, device):
+    """The device workspace of the kernel call for n samples (initialised by every call itself)."""
+    return torch.empty(lib.transoar_augment_intensity_workspace_bytes(int(n)) // 4, dtype=torch.int32, device=device)
+
+
+def intensity_into(image, image_out, table, steps, scratch=None, workspace=None):
+    """The kernel sequence on the current stream: image (N, [1,] D, H, W) fp32 -> image_out (the same shape; may be `image`),
+    table a DEVICE table (N, 12) int32, steps the union of the flags the table may carry, scratch a device tensor of the image's
+    size (needed with SMOOTH in steps) and workspace from intensity_workspace; both are allocated here when not given (do give
+    them under capture).  Capturable; nothing is read back."""
+    img, out = _volume(image, "image"), _volume(image_out, "image_out")
+    assert usable(img), "intensity_into: an fp32 CUDA image"
+    assert img.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.shape == img.shape and out.device == img.device
+    n, d, h, w = img.shape
+    _tail_table(table, n)
+    assert table.is_cuda and table.is_contiguous()
+    steps = int(steps) & (NOISE | SMOOTH | CONTRAST)
+    if steps & SMOOTH:
+        if scratch is None:
+            scratch = torch.empty_like(img)
+        assert scratch.is_cuda and scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= img.numel()
+        assert scratch.data_ptr() not in (img.data_ptr(), out.data_ptr())
+    if workspace is None:
+        workspace = intensity_workspace(n, img.device)
+    assert workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= \
+        lib.transoar_augment_intensity_workspace_bytes(n)
+    _native.launch(lib.transoar_augment_intensity, img, img.data_ptr(), out.data_ptr(), _native.ptr(scratch) if steps & SMOOTH else None,
+                   n, d, h, w, table.data_ptr(), steps, workspace.data_ptr())
+    return image_out
 
 
 # ---- the reference's configuration -> tables -------------------------------------------------------------------------------------
@@ -282,18 +469,31 @@ class BatchAugment:
     resizes them first as the reference's 'test' chain does.  On CUDA inputs a call draws on the host, copies the table from a pinned slot without blocking
     and launches: no host synchronisation per batch.  The pinned slots form a ring with one event each (recorded after the launch
     that reads the slot's table), waited on only when the ring wraps, so a draw never overwrites memory an earlier copy or launch
-    may still be reading."""
+    may still be reading.
+
+    full_chain=True ('train' only; 'val' and 'test' are unaffected) also takes p_shear, p_gaussian_noise, p_gaussian_smooth and
+    p_adjust_contrast above 0.  Their parameters come from a SECOND generator seeded from `seed`, so the draws of the other steps
+    and the spatial table are those of full_chain=False for the same seed.  Shear goes into the affine table.  When one of the
+    three intensity probabilities is above 0 the intensity tail runs after the resample, in the reference's order noise -> smooth
+    -> gain -> offset -> contrast: the resample's table then carries gain 1 and offset 0 and the tail's table (N, 12) the drawn
+    ones; it is uploaded through a pinned ring of its own, the scratch volume and the workspace are kept per (device, shape), and
+    the tail works in place on the resample's output (`out=` included).  Otherwise no tail is launched."""
 
     SLOTS = 4
 
-    def __init__(self, config, split="train", seed=0, deterministic=False):
+    def __init__(self, config, split="train", seed=0, deterministic=False, full_chain=False):
         if split not in ("train", "val", "test"):
             raise ValueError("Please use 'test', 'val', or 'train' as split arg.")
         a = config["augmentation"]
-        if split == "train":
+        self.full_chain = bool(full_chain) and split == "train"
+        self.tail_steps = 0
+        if split == "train" and not self.full_chain:
             for key in UNSUPPORTED:
                 if float(a.get(key, 0) or 0) > 0:
-                    raise ValueError("augmentation.%s = %r: not implemented on the device (only 0 is supported)" % (key, a[key]))
+                    raise ValueError("augmentation.%s = %r: not part of the default device chain (only 0 is supported); "
+                                     "BatchAugment(..., full_chain=True) implements it" % (key, a[key]))
+        if self.full_chain:
+            self._read_full_chain(a)
         self.split, self.deterministic, self.aug = split, bool(deterministic), a
         stats = config["foreground_voxel_statistics"]
         self.a_min, self.a_max = _f32(stats["percentile_00_5"]), _f32(stats["percentile_99_5"])
@@ -304,7 +504,41 @@ class BatchAugment:
         self.out_shape = tuple(int(round(s)) for s in (median if patch is None else patch))
         self.translate_range = [m * float(a.get("translate_precentage", 0)) / 100 for m in median]
         self.generator = torch.Generator().manual_seed(int(seed))
-        self._slots = {}
+        self.generator2 = torch.Generator().manual_seed((int(seed) + 0x9E3779B97F4A7C15) % (2 ** 63))      # shear and the tail
+        self._slots, self._tail_slots, self._buffers = {}, {}, {}
+
+    def _read_full_chain(self, a):
+        """The ranges of the four opt-in steps, refused by key name where the kernels (or MONAI) would not take them."""
+        on = lambda key: float(a.get(key, 0) or 0) > 0
+        self.tail_steps = (NOISE if on("p_gaussian_noise") else 0) | (SMOOTH if on("p_gaussian_smooth") else 0) | \
+            (CONTRAST if on("p_adjust_contrast") else 0)
+        self.noise_mean, self.noise_std = float(a.get("gaussian_noise_mean", 0.0)), float(a.get("gaussian_noise_std", 0.1))
+        if not math.isfinite(self.noise_mean) or not math.isfinite(self.noise_std) or self.noise_std < 0:
+            raise ValueError("augmentation.gaussian_noise_std = %r (mean %r): a finite mean and a finite std >= 0"
+                             % (a.get("gaussian_noise_std"), a.get("gaussian_noise_mean")))
+        self.sigma = tuple(float(x) for x in a.get("gaussian_smooth_sigma", (0.5, 1.0)))
+        if len(self.sigma) != 2 or not 0 < self.sigma[0] <= self.sigma[1] <= MAX_SIGMA:
+            raise ValueError("augmentation.gaussian_smooth_sigma = %r: a range (lo, hi) with 0 < lo <= hi <= %g (a radius of at most "
+                             "16 voxels)" % (a.get("gaussian_smooth_sigma"), MAX_SIGMA))
+        self.gamma = tuple(float(x) for x in a.get("adjust_contrast_gamma", (0.5, 4.5)))
+        if len(self.gamma) != 2 or not 0 < self.gamma[0] <= self.gamma[1] < math.inf:
+            raise ValueError("augmentation.adjust_contrast_gamma = %r: a range (lo, hi) with 0 < lo <= hi" % (a.get("adjust_contrast_gamma"),))
+        shear = list(a.get("shear_range", ()) or ())
+        if len(shear) > 6:
+            raise ValueError("augmentation.shear_range = %r: at most six entries" % (a.get("shear_range"),))
+        self.shear_range = []
+        for entry in shear + [0.0] * (6 - len(shear)):                   # padded with zeros; f -> U(-f, f), (a, b) -> U(a, b)
+            lo, hi = (float(entry[0]), float(entry[1])) if isinstance(entry, (list, tuple)) else (-abs(float(entry)), abs(float(entry)))
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+                raise ValueError("augmentation.shear_range = %r: finite entries f or pairs (a, b) with a <= b" % (a.get("shear_range"),))
+            self.shear_range.append((lo, hi))
+
+    def _uniform2(self, n, lo, hi, width=None):
+        shape = (n,) if width is None else (n, width)
+        return lo + (hi - lo) * torch.rand(shape, dtype=torch.float64, generator=self.generator2)
+
+    def _applied2(self, n, key):
+        return torch.rand(n, dtype=torch.float64, generator=self.generator2) < float(self.aug.get(key, 0) or 0)
 
     def _uniform(self, n, lo, hi, width=None):
         shape = (n,) if width is None else (n, width)
@@ -347,12 +581,49 @@ class BatchAugment:
             steps["crop"] = (room // 2).expand(n, 3).clone()
         else:
             steps["crop"] = torch.floor(self._uniform(n, 0.0, 1.0, 3) * (room + 1)).clamp(max=room)
+        if self.full_chain and float(self.aug.get("p_shear", 0) or 0) > 0:
+            on = self._applied2(n, "p_shear")
+            lo = torch.tensor([r[0] for r in self.shear_range], dtype=torch.float64)
+            hi = torch.tensor([r[1] for r in self.shear_range], dtype=torch.float64)
+            steps["shear"] = torch.where(on[:, None], lo + (hi - lo) * self._uniform2(n, 0.0, 1.0, 6), torch.zeros(n, 6, dtype=torch.float64))
         return steps
+
+    def sample_intensity(self, n, gain=None, offset=None):
+        """The drawn tail of n samples, as compose_intensity takes it (gain and offset are those of sample())."""
+        flags = torch.zeros(n, dtype=torch.int64)
+        on = self._applied2(n, "p_gaussian_noise")
+        std = torch.where(on, self._uniform2(n, 0.0, self.noise_std), torch.zeros(n, dtype=torch.float64))
+        flags |= on.to(torch.int64) * NOISE
+        on = self._applied2(n, "p_gaussian_smooth")
+        sigma = self._uniform2(n, self.sigma[0], self.sigma[1], 3)
+        flags |= on.to(torch.int64) * SMOOTH
+        on = self._applied2(n, "p_adjust_contrast")
+        gamma = torch.where(on, self._uniform2(n, self.gamma[0], self.gamma[1]), torch.ones(n, dtype=torch.float64))
+        flags |= on.to(torch.int64) * CONTRAST
+        keys = torch.randint(0, 2 ** 32, (n, 2), dtype=torch.int64, generator=self.generator2)
+        return dict(flags=flags, noise_mean=self.noise_mean, noise_std=std, sigma=sigma, gamma=gamma, keys=keys,
+                    gain=1.0 if gain is None else gain, offset=0.0 if offset is None else offset)
+
+    def draw_both(self, n, in_shape=None):
+        """-> (the table (n, 16) fp32, the tail's table (n, 12) int32 or None when no tail runs) of n freshly drawn samples."""
+        in_shape = self.out_shape if in_shape is None else tuple(int(s) for s in in_shape)
+        steps = self.sample(n, in_shape)
+        tail = None
+        if self.tail_steps:
+            tail = compose_intensity(n, **self.sample_intensity(n, steps["gain"], steps["offset"]))
+            steps["gain"], steps["offset"] = torch.ones(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+        return check_table(compose_params(n, in_shape, **steps)), tail
 
     def draw(self, n, in_shape=None):
         """-> the table (n, 16) fp32 of n freshly drawn samples (a CPU tensor)."""
-        in_shape = self.out_shape if in_shape is None else tuple(int(s) for s in in_shape)
-        return check_table(compose_params(n, in_shape, **self.sample(n, in_shape)))
+        return self.draw_both(n, in_shape)[0]
+
+    def _tail_buffers(self, out):
+        """The scratch volume and the workspace of the tail, kept per (device, shape)."""
+        key = (out.device, tuple(out.shape))
+        if key not in self._buffers:
+            self._buffers[key] = (torch.empty_like(out) if self.tail_steps & SMOOTH else None, intensity_workspace(out.shape[0], out.device))
+        return self._buffers[key]
 
     def _upload(self, table, device):
         """-> (the table on `device`, copied from a pinned slot of the ring without blocking; the slot's event, to be recorded
@@ -363,11 +634,24 @@ class BatchAugment:
         img = _volume(image, "image")
         n = img.shape[0]
         lab = None if labels is None else _volume(labels, "labels")
-        table, event = self.draw(n, img.shape[1:]), None
+        (table, tail), event, tail_event = self.draw_both(n, img.shape[1:]), None, None
         if usable(img, lab):
             with torch.cuda.device(img.device):
                 table, event = self._upload(table, img.device)
+                if tail is not None:
+                    tail, tail_event = upload_through_ring(self._tail_slots, self.SLOTS, tail, img.device)
         got = augment(img[:, None], None if lab is None else lab[:, None], table, self.out_shape, self.a_min, self.a_max, out=out)
         if event is not None:
             event.record(torch.cuda.current_stream(img.device))
+        if tail is not None:
+            x = got[0]
+            if tail_event is not None:
+                with torch.cuda.device(img.device):
+                    scratch, workspace = self._tail_buffers(_volume(x, "image"))
+                    intensity_into(x, x, tail, self.tail_steps, scratch, workspace)
+                    tail_event.record(torch.cuda.current_stream(img.device))
+            else:
+                x.copy_(intensity_torch(x, tail.to(x.device)))
+                if tail_event is not None:
+                    tail_event.record(torch.cuda.current_stream(img.device))
         return got
