@@ -36,6 +36,12 @@ LIBS = {
     "libtransoar_deteval.so": ["det_eval.hip"],
     "libtransoar_augment.so": ["augment.hip"],
     "libtransoar_resize.so": ["resize.hip"],
+    "libtransoar_denseattn.so": ["dense_attn.hip"],
+}
+# per-library flags on top of COMMON_FLAGS
+EXTRA_FLAGS = {
+    # plain fp32 VALU code only: the compiler may not fuse pairs of fp32 operations into v_pk_*_f32
+    "libtransoar_denseattn.so": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 
@@ -79,7 +85,7 @@ def is_stale(name):
 
 
 def _compile(name, verbose):
-    cmd = [HIPCC] + COMMON_FLAGS + [os.path.join(CSRC, s) for s in LIBS[name]] + ["-o", lib_path(name)]
+    cmd = [HIPCC] + COMMON_FLAGS + EXTRA_FLAGS.get(name, []) + [os.path.join(CSRC, s) for s in LIBS[name]] + ["-o", lib_path(name)]
     if len(LIBS[name]) == 1:
         cmd += ["-MD", "-MF", _dep_path(name)]
     elif os.path.exists(_dep_path(name)):

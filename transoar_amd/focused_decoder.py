@@ -30,7 +30,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import roi_attn, rows, shadow
+from . import dense_attn, roi_attn, rows, shadow
 from . import tokens as fused_tokens
 from .position_encoding import is_constant
 from .token_linear import token_linear
@@ -256,9 +256,22 @@ class FocusedAttn(nn.Module):
             out = out + shadow.as_dtype(self.v_proj.bias, out.dtype).view(h, hd)
         return out.reshape(b, n_q, c)
 
-    def forward(self, q, k, v, mask=None, need_weights=False, roi=None, k_pos=None, roi_cache=None):
+    def _key_bits(self, mask, key_mask, n_org, n_q, n_kv):
+        """The mask in the form of the dense kernels (dense_attn.key_bits), or False when they cannot express it."""
+        if key_mask is None:
+            return None if mask is None else False
+        if tuple(key_mask.shape) != (n_q, n_kv) or key_mask.dtype != torch.bool:
+            return False
+        try:
+            return dense_attn.key_bits(key_mask, n_org)
+        except ValueError:          # rows of an organ differ, or an organ without a key (NaN in the reference: keep its route)
+            return False
+
+    def forward(self, q, k, v, mask=None, need_weights=False, roi=None, k_pos=None, roi_cache=None, key_mask=None,
+                n_org=1):
         """q (B,Nq,C), k/v (B,Nkv,C); mask additive (Nq,Nkv) of 0/-inf; roi: the
-        same mask as per-organ key lists.  k_pos: if given, the keys are
+        same mask as per-organ key lists; key_mask: the same mask as booleans (True = masked, n_org organs of
+        equal query counts), for the fused dense path.  k_pos: if given, the keys are
         ``v + k_pos`` and ``k`` may be None.  Returns (out, weights or None)."""
         if roi is not None and not need_weights and (k_pos is not None or k is v):
             x = self._roi_attention(q, v, k_pos, roi, roi_cache)
@@ -268,9 +281,19 @@ class FocusedAttn(nn.Module):
         b, n_kv, c = k.shape
         n_q = q.shape[1]
         h, hd = self.num_heads, c // self.num_heads
-        kh = self.k_proj(k).view(b, n_kv, h, hd).transpose(1, 2)
-        vh = self.v_proj(v).view(b, n_kv, h, hd).transpose(1, 2)
-        qh = self.k_proj(q).view(b, n_q, h, hd).transpose(1, 2)     # sic: k_proj
+        kp, vp, qp = self.k_proj(k), self.v_proj(v), self.k_proj(q)     # sic: k_proj
+        if not need_weights and self.pos_bias is None and not (self.training and self.attn_drop.p > 0) \
+                and dense_attn.usable(qp, kp, vp, h):
+            bits = self._key_bits(mask, key_mask, n_org, n_q, n_kv)
+            if bits is not False:
+                # flash attention over the 48-column head slices of the projections as they lie in memory: no head
+                # copies, no (Nq, Nkv) additive mask (csrc/dense_attn.hip)
+                with torch.autocast(q.device.type, enabled=False):
+                    x = dense_attn.dense_attention(qp, kp, vp, bits, self.scale)
+                return self.proj_drop(self.proj(x)), None
+        kh = kp.view(b, n_kv, h, hd).transpose(1, 2)
+        vh = vp.view(b, n_kv, h, hd).transpose(1, 2)
+        qh = qp.view(b, n_q, h, hd).transpose(1, 2)
         bias = mask() if callable(mask) else mask          # the dense additive mask is built lazily (221 MB)
         if self.pos_bias is not None:
             bias = self.pos_bias if bias is None else bias + self.pos_bias
@@ -395,7 +418,8 @@ class FocusedDecoderLayer(nn.Module):
         q = tgt if query_pos is None else tgt + query_pos
         roi = (self.roi_index, self.roi_pad, self.roi_inv_ptr, self.roi_inv_idx) if self._use_roi else None
         ca, weights = self.cross_attn(q, None if src_pos is not None else src, src, mask=self._dense_bias,
-                                      need_weights=need_weights, roi=roi, k_pos=src_pos, roi_cache=roi_cache)
+                                      need_weights=need_weights, roi=roi, k_pos=src_pos, roi_cache=roi_cache,
+                                      key_mask=self.attn_mask, n_org=self.config["num_organs"])
         tgt, tgt16 = self._add_norm(tgt, ca, self.norm1, self.dropout1)
 
         # the fused pass also returns the bf16 rounding the FFN's first GEMM would make of tgt
