@@ -19,7 +19,7 @@ CASES = [  # N, Cin, Cout, D, H, W, stride, bias
     (1, 96, 96, 5, 5, 8, 1, False), (1, 96, 384, 4, 4, 8, 1, True), (2, 8, 40, 3, 7, 24, 1, True),
     (1, 1, 24, 6, 10, 16, 1, False), (1, 192, 64, 2, 2, 8, 1, True),
     (2, 24, 24, 3, 4, 64, 1, False), (1, 8, 32, 2, 3, 128, 1, False), (1, 32, 16, 3, 2, 64, 1, False),   # LDS-transposed wgrad
-    (1, 48, 48, 3, 3, 64, 1, False), (1, 40, 64, 2, 2, 64, 1, True),    # ... in 32-channel blocks
+    (1, 48, 48, 3, 3, 64, 1, False), (1, 40, 64, 2, 2, 64, 1, True),    # W % 64 == 0 but > 32 channels and few rows: the voxel-major wgrad
     (2, 1, 32, 3, 4, 32, 1, False), (1, 1, 8, 2, 3, 48, 1, False), (3, 1, 24, 5, 3, 16, 1, False),   # Cin=1: MFMA weight gradient
     # >= 2^16 voxels, stride 1, <= 24 -> <= 32 channels: the LDS halo-tile kernel, partial tiles on every axis
     (1, 24, 24, 18, 22, 200, 1, False), (1, 8, 32, 20, 30, 120, 1, True), (2, 16, 24, 17, 33, 136, 1, False),
@@ -84,7 +84,7 @@ def _gpu_relerr(a, b):
                                   (2, 384, 384, 10, 10, 16, 1), (2, 384, 768, 10, 10, 16, 2), (2, 768, 768, 5, 5, 8, 1),
                                   (2, 96, 384, 40, 40, 64, 1), (2, 384, 384, 5, 5, 8, 1),
                                   # AMOS geometry at its reference batch (round-3 ADVICE): 2 x 128 x 128 x 64 = 2^21 output
-                                  # rows, one more than an implicit-GEMM launch addresses -> batch ranges (conv_gemm._batch_chunks)
+                                  # rows, one more than an implicit-GEMM launch addresses -> batch ranges (conv_plan.batch_ranges)
                                   (2, 24, 48, 256, 256, 128, 2), (2, 48, 48, 128, 128, 64, 1)])
 def test_conv3d_k3_flagship_layer_shapes(case):
     if not torch.cuda.is_available():

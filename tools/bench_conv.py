@@ -8,6 +8,8 @@ os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(ROOT, "tools", "miopen
 import torch
 import torch.nn.functional as F
 from transoar_amd import conv3d as C
+from transoar_amd.conv_gemm import pack_dgrad, pack_fwd
+from transoar_amd.conv_plan import plan_conv
 
 LAYERS = [  # name, Cin, Cout, D, H, W (input), stride
     ("s0c1", 1, 24, 160, 160, 256, 1), ("s0c2", 24, 24, 160, 160, 256, 1), ("s1c1", 24, 48, 160, 160, 256, 2),
@@ -33,13 +35,13 @@ for name, ci, co, d, h, w, s in LAYERS:
     wt = torch.randn(co, ci, 3, 3, 3, device="cuda") * 0.05
     res = {"layer": name, "shape": [ci, co, d, h, w, s]}
     if ci > 1:
-        wk = C._pack_taps(wt)
+        wk = pack_fwd(wt)
         y = C.conv3d_k3_forward(x, wk, None, s)
         res["hip_fwd"] = round(t_ms(lambda: C.conv3d_k3_forward(x, wk, None, s)), 3)
         gy = torch.randn_like(y)
-        wtr = wt.flip(2, 3, 4).permute(2, 3, 4, 1, 0).reshape(27, ci, co).to(torch.bfloat16).contiguous()
+        wtr = pack_dgrad(wt.flip(2, 3, 4))
         res["hip_dgrad"] = round(t_ms(lambda: C.conv3d_k3_forward(gy, wtr, None, 1, dilated_input=(s == 2))), 3)
-        if s == 1 and C.lds_wgrad_supported(x, gy):
+        if plan_conv(2, ci, co, d, h, w, s).wgrad in ("lds_tr", "lds"):
             res["hip_wgrad_lds"] = round(t_ms(lambda: C.conv3d_k3_wgrad_lds(x, gy)), 3)     # what the model runs
         else:
             res["hip_wgrad_v1"] = round(t_ms(lambda: C.conv3d_k3_wgrad(x, gy, s)), 3)      # off by default

@@ -4,6 +4,7 @@ import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from transoar_amd import conv3d as C
+from transoar_amd.conv_gemm import pack_fwd
 
 
 def t_ms(fn, n=10):
@@ -21,7 +22,7 @@ for ci in (24, 1):
     if ci > 1:
         x = x.contiguous(memory_format=torch.channels_last_3d)
     wt = torch.randn(24, ci, 3, 3, 3, device="cuda") * 0.05
-    wk = C._pack_taps(torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 0, 0, 7)) if ci == 1 else wt)
+    wk = pack_fwd(torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, 0, 0, 7)) if ci == 1 else wt)
     plain = t_ms(lambda: C.conv3d_k3_forward_c1(x, wk, None) if ci == 1 else C.conv3d_k3_forward(x, wk, None, 1))
     stats = t_ms(lambda: C.conv3d_k3_forward_stats(x, wk, None))
     print(json.dumps({"cin": ci, "plain_ms": round(plain, 4), "with_stats_ms": round(stats, 4)}))

@@ -9,11 +9,13 @@ import os
 import torch
 
 from . import _native
+from . import conv_plan as _plan
 from ._native import launch, ptr
 
 ABI_VERSION = 3
 CL3D = torch.channels_last_3d
 lib = _native.bind("convgemm", abi=ABI_VERSION)
+DGRAD_S2_HALO = _plan.KNOBS.dgrad_s2_halo          # read by tests; the switch itself lives in conv_plan.KNOBS
 
 
 def _taps(entries):
@@ -28,11 +30,6 @@ TAPS_FWD = _taps([(-1, 0), (0, 1), (1, 2)])        # source = s*m + t - 1
 TAPS_DGRAD1 = _taps([(1, 0), (0, 1), (-1, 2)])     # source = m + 1 - t
 TAPS_PARITY = (_taps([(0, 1)]), _taps([(1, 0), (0, 2)]))     # dx voxel 2m + p: p = 0 sees tap 1 of dy m; p = 1 taps 0, 2 of dy m+1, m
 TAPS_ONE = _taps([(0, 1)])
-
-# launches with fewer output tiles than this split their K steps (per-split partial maps + a finish pass)
-SPLIT_BELOW_TILES = 384
-DGRAD_S2_HALO = os.environ.get("TRANSOAR_DGRAD_S2_HALO", "1") != "0"
-WGRAD_BLOCKS = 512          # workgroups of a weight-gradient launch: one resident set (2 per CU); 2x for very long or very wide problems
 
 
 def pack_fwd(weight):
@@ -93,17 +90,6 @@ class PackPlan:
             m._packs, m._packs_version = packs, m.weight._version
 
 
-def _split_for(tiles, k_steps):
-    if tiles >= SPLIT_BELOW_TILES:
-        return 1
-    return max(1, min((SPLIT_BELOW_TILES + tiles - 1) // tiles, k_steps // 4, 16))
-
-
-def _tiles(rows, cout):
-    bn = 64 if cout <= 64 else 128
-    return ((rows + 127) // 128) * ((cout + bn - 1) // bn)
-
-
 def _igemm(x, wk, bias, out, src_dims, cin, cout, m_dims, src_stride, out_dims, out_stride, parity, taps, n, split, classes=0):
     """One launch of transoar_conv3d_igemm (+ the summing / cast pass when split > 1); `out` is the whole output map."""
     if split > 1:
@@ -117,78 +103,60 @@ def _igemm(x, wk, bias, out, src_dims, cin, cout, m_dims, src_stride, out_dims, 
                *m_dims, src_stride, *out_dims, out_stride, *parity, *taps, 1, classes)
 
 
-MAX_ROWS = 1 << 21          # rows (voxels of the row space) per launch: the kernels decompose a row index with float reciprocals
+def _batch(ranges, n, *tensors):
+    """(count, split or chunks, the tensors' views of the batch range) of every range of a plan."""
+    for i, c, k in ranges:
+        yield (c, k) + (tensors if c == n else tuple(t[i:i + c] for t in tensors))
 
 
-def _batch_chunks(n, rows_per_sample, what):
-    """Batch ranges [(first, count), ...] whose row count stays below MAX_ROWS (one range when the whole batch fits).
-    A channels-last (N, C, D, H, W) tensor sliced along N is still a dense channels-last tensor, so a range is just
-    another launch on a view.  AMOS at its reference batch (2 x 128 x 128 x 64 = 2^21 rows at stage 1) needs this."""
-    if n * rows_per_sample < MAX_ROWS:
-        return [(0, n)]
-    per = (MAX_ROWS - 1) // rows_per_sample
-    if per < 1:
-        raise RuntimeError("%s: one sample has %d rows, the implicit-GEMM kernels address < %d per launch"
-                           % (what, rows_per_sample, MAX_ROWS))
-    return [(i, min(per, n - i)) for i in range(0, n, per)]
-
-
-def conv_forward(x, wk, bias, stride, split=None):
-    """x (N, Cin, D, H, W) NDHWC bf16, wk (27, Cout, Cin) bf16, bias fp32 or None -> (N, Cout, Do, Ho, Wo) NDHWC bf16."""
+def conv_forward(x, wk, bias, stride, split=None, ranges=None):
+    """x (N, Cin, D, H, W) NDHWC bf16, wk (27, Cout, Cin) bf16, bias fp32 or None -> (N, Cout, Do, Ho, Wo) NDHWC bf16.
+    split: the split-K factor instead of the plan's; ranges: conv_plan.igemm_ranges of the shape, when the caller has them."""
     n, ci, d, h, w = x.shape
     co = wk.shape[1]
     od, oh, ow = (d - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1
-    chunks = _batch_chunks(n, od * oh * ow, "conv_forward")
-    if len(chunks) > 1:
-        y = torch.empty((n, co, od, oh, ow), dtype=torch.bfloat16, device=x.device, memory_format=CL3D)
-        for i, c in chunks:
-            y[i:i + c] = conv_forward(x[i:i + c], wk, bias, stride, split)
-        return y
     y = torch.empty((n, co, od, oh, ow), dtype=torch.bfloat16, device=x.device, memory_format=CL3D)
-    if split is None:
-        split = _split_for(_tiles(n * od * oh * ow, co), (27 * ci + 63) // 64)
-    _igemm(x, wk, bias, y, (d, h, w), ci, co, (od, oh, ow), stride, (od, oh, ow), 1, (0, 0, 0), (TAPS_FWD,) * 3, n, split)
+    for c, s, xs, ys in _batch(ranges or _plan.igemm_ranges(n, od * oh * ow, ci, co, 27, "conv_forward"), n, x, y):
+        _igemm(xs, wk, bias, ys, (d, h, w), ci, co, (od, oh, ow), stride, (od, oh, ow), 1, (0, 0, 0), (TAPS_FWD,) * 3, c, split or s)
     return y
 
 
-def conv_dgrad(gy, wkt, stride, in_dims, split=None):
-    """gy (N, Cout, Do, Ho, Wo) NDHWC bf16, wkt (27, Cin, Cout) bf16 -> dx (N, Cin, D, H, W) NDHWC bf16."""
+def dgrad_s2_halo(gy, wkt, in_dims):
+    """Stride 2, few input channels: dx as whole lines, all eight parity classes of a tile in one workgroup."""
     n, co, od, oh, ow = gy.shape
     ci = wkt.shape[1]
-    d, h, w = in_dims
-    gx = torch.empty((n, ci, d, h, w), dtype=torch.bfloat16, device=gy.device, memory_format=CL3D)
-    halo = split is None and stride == 2 and DGRAD_S2_HALO and ci <= 32 and co in (16, 32, 48)
-    chunks = [(0, n)] if halo else _batch_chunks(n, d * h * w, "conv_dgrad")
-    if len(chunks) > 1:
-        for i, c in chunks:
-            gx[i:i + c] = conv_dgrad(gy[i:i + c], wkt, stride, in_dims, split)
-        return gx
-    if stride == 1:
-        if split is None:
-            split = _split_for(_tiles(n * d * h * w, ci), (27 * co + 63) // 64)
-        _igemm(gy, wkt, None, gx, (od, oh, ow), co, ci, (d, h, w), 1, (d, h, w), 1, (0, 0, 0), (TAPS_DGRAD1,) * 3, n, split)
-        return gx
-    if split is None and DGRAD_S2_HALO and ci <= 32 and co in (16, 32, 48):
-        # few input channels, full-resolution dx: one workgroup computes all eight parity classes of a dx tile (HBM bound)
-        launch(lib.transoar_conv3d_dgrad_s2_halo, gy, gy.data_ptr(), wkt.data_ptr(), gx.data_ptr(), n, od, oh, ow, d, h, w, ci, co)
-        return gx
-    # stride 2: the eight parity classes (pd, ph, pw) of the dx voxels in one launch: 1, 2, 4 or 8 taps each
-    if split is None:
-        split = _split_for(_tiles(n * d * h * w, ci), (8 * co + 63) // 64)      # K steps of the eight-tap class
-    _igemm(gy, wkt, None, gx, (od, oh, ow), co, ci, (1, 1, 1), 1, (d, h, w), 2, (0, 0, 0), (TAPS_ONE,) * 3, n, split, classes=1)
+    gx = torch.empty((n, ci) + tuple(in_dims), dtype=torch.bfloat16, device=gy.device, memory_format=CL3D)
+    launch(lib.transoar_conv3d_dgrad_s2_halo, gy, gy.data_ptr(), wkt.data_ptr(), gx.data_ptr(), n, od, oh, ow, *in_dims, ci, co)
     return gx
 
 
-def _wgrad(x2, gy2, geom, taps, taps_out, out_shape):
+def dgrad_igemm(gy, wkt, stride, in_dims, ranges, split=None):
+    """The implicit-GEMM data gradient: stride 1 with the mirrored tap list; stride 2 the eight parity classes (pd, ph, pw)
+    of the dx voxels in one launch."""
+    n, co, od, oh, ow = gy.shape
+    ci = wkt.shape[1]
+    dims = tuple(in_dims)
+    gx = torch.empty((n, ci) + dims, dtype=torch.bfloat16, device=gy.device, memory_format=CL3D)
+    for c, s, gys, gxs in _batch(ranges, n, gy, gx):
+        if stride == 1:
+            _igemm(gys, wkt, None, gxs, (od, oh, ow), co, ci, dims, 1, dims, 1, (0, 0, 0), (TAPS_DGRAD1,) * 3, c, split or s)
+        else:
+            _igemm(gys, wkt, None, gxs, (od, oh, ow), co, ci, (1, 1, 1), 1, dims, 2, (0, 0, 0), (TAPS_ONE,) * 3, c, split or s, classes=1)
+    return gx
+
+
+def conv_dgrad(gy, wkt, stride, in_dims, split=None):
+    """gy (N, Cout, Do, Ho, Wo) NDHWC bf16, wkt (27, Cin, Cout) bf16 -> dx (N, Cin, D, H, W) NDHWC bf16.
+    split: that split-K factor on the implicit GEMM (stride 2: the parity-class launch, never the halo-tile kernel)."""
+    route, ranges = _plan.dgrad_gemm(gy.shape[0], wkt.shape[1], gy.shape[1], *in_dims, stride, general=split is not None)
+    if route == "s2_halo":
+        return dgrad_s2_halo(gy, wkt, in_dims)
+    return dgrad_igemm(gy, wkt, stride, in_dims, ranges, split)
+
+
+def _wgrad(x2, gy2, geom, taps, taps_out, out_shape, chunks=None):
     n, sd, sh, sw, ci, co, md, mh, mw, stride = geom
-    nt = 1
-    for t in taps:
-        nt *= t & 3
-    bt = 64 if (ci <= 64 and co <= 64) else 128
-    tiles = nt * ((co + bt - 1) // bt) * ((ci + bt - 1) // bt)
-    rows = n * md * mh * mw
-    budget = WGRAD_BLOCKS * (2 if (rows >= (1 << 20) or tiles >= 64) else 1)      # tools/tune_wgrad.py
-    chunks = max(1, min(budget // tiles, rows // 1024 if rows >= 1024 else 1))      # >= 16 K steps of 64 rows per block
+    chunks = chunks or _plan.wgrad_chunks(n * md * mh * mw, ci, co, taps_out)
     part = torch.empty(lib.transoar_conv3d_wgrad_part_floats(ci, co, chunks, taps_out), dtype=torch.float32, device=x2.device)
     dw = torch.empty(out_shape, dtype=torch.float32, device=x2.device)
     launch(lib.transoar_conv3d_wgrad, x2, gy2.data_ptr(), x2.data_ptr(), part.data_ptr(), dw.data_ptr(), n, sd, sh, sw, ci, co,
@@ -196,21 +164,11 @@ def _wgrad(x2, gy2, geom, taps, taps_out, out_shape):
     return dw
 
 
-WGRAD_RING = os.environ.get("TRANSOAR_WGRAD_RING", "1") != "0"
-WGRAD_RING_CHUNKS = 85           # workgroups per filter plane of a ring launch: 3 x 85 = one 512-thread workgroup per CU
-
-
-def wgrad_ring_supported(ci, co, ow, rows):
-    """The LDS-ring weight gradient (conv_wgrad_ring.hpp): up to 64 channels on either side and more than 32 on at least
-    one, W-rows of dy in 64-voxel units, enough voxels to keep one persistent workgroup per CU busy."""
-    return (WGRAD_RING and ci <= 64 and co <= 64 and max(ci, co) > 32 and ci % 8 == 0 and co % 8 == 0 and ow % 64 == 0
-            and rows >= (1 << 18))
-
-
 def conv_wgrad_ring(x, gy, stride, chunks=None):
+    """The LDS-ring weight gradient (conv_wgrad_ring.hpp); conv_plan.wgrad_gemm says which layers take it."""
     n, ci, d, h, w = x.shape
     co, od, oh, ow = gy.shape[1:]
-    chunks = chunks or WGRAD_RING_CHUNKS
+    chunks = chunks or _plan.WGRAD_RING_CHUNKS
     part = torch.empty(lib.transoar_conv3d_wgrad_part_floats(ci, co, chunks, 27), dtype=torch.float32, device=x.device)
     dw = torch.empty((co, ci, 3, 3, 3), dtype=torch.float32, device=x.device)
     launch(lib.transoar_conv3d_wgrad_ring, x, gy.data_ptr(), x.data_ptr(), part.data_ptr(), dw.data_ptr(), n, d, h, w, ci, co,
@@ -218,20 +176,21 @@ def conv_wgrad_ring(x, gy, stride, chunks=None):
     return dw
 
 
-def conv_wgrad(x, gy, stride):
-    """x (N, Cin, D, H, W), gy (N, Cout, Do, Ho, Wo) NDHWC bf16 -> dW (Cout, Cin, 3, 3, 3) fp32."""
+def wgrad_voxel_major(x, gy, stride, ranges):
+    """The general voxel-major weight gradient, one launch per batch range: the filter gradient is a sum over samples."""
     n, ci, d, h, w = x.shape
     co, od, oh, ow = gy.shape[1:]
-    if wgrad_ring_supported(ci, co, ow, n * od * oh * ow):
-        return conv_wgrad_ring(x, gy, stride)
-    chunks = _batch_chunks(n, od * oh * ow, "conv_wgrad")
-    if len(chunks) > 1:          # the filter gradient is a sum over samples
-        dw = None
-        for i, c in chunks:
-            part = conv_wgrad(x[i:i + c], gy[i:i + c], stride)
-            dw = part if dw is None else dw.add_(part)
-        return dw
-    return _wgrad(x, gy, (n, d, h, w, ci, co, od, oh, ow, stride), (TAPS_FWD,) * 3, 27, (co, ci, 3, 3, 3))
+    dw = None
+    for c, chunks, xs, gys in _batch(ranges, n, x, gy):
+        part = _wgrad(xs, gys, (c, d, h, w, ci, co, od, oh, ow, stride), (TAPS_FWD,) * 3, 27, (co, ci, 3, 3, 3), chunks)
+        dw = part if dw is None else dw.add_(part)
+    return dw
+
+
+def conv_wgrad(x, gy, stride):
+    """x (N, Cin, D, H, W), gy (N, Cout, Do, Ho, Wo) NDHWC bf16 -> dW (Cout, Cin, 3, 3, 3) fp32."""
+    route, detail = _plan.wgrad_gemm(x.shape[0], x.shape[1], *gy.shape[1:])
+    return conv_wgrad_ring(x, gy, stride) if route == "ring" else wgrad_voxel_major(x, gy, stride, detail)
 
 
 def linear_wgrad(x, gy):
@@ -250,10 +209,7 @@ def linear_wgrad_bias(x, gy):
     """x (T, K), gy (T, N) bf16 contiguous -> (dW (N, K), db (N,)) fp32 = (gy^T x, gy.sum(0)) in one pass over gy."""
     t, k = x.shape
     nn_ = gy.shape[1]
-    bt = 64 if (k <= 64 and nn_ <= 64) else 128
-    tiles = ((nn_ + bt - 1) // bt) * ((k + bt - 1) // bt)
-    budget = WGRAD_BLOCKS * (2 if (t >= (1 << 20) or tiles >= 64) else 1)
-    chunks = max(1, min(budget // tiles, t // 1024 if t >= 1024 else 1))
+    chunks = _plan.wgrad_chunks(t, k, nn_, 1)
     part = torch.empty(lib.transoar_conv3d_wgrad_part_floats(k, nn_, chunks, 1), dtype=torch.float32, device=x.device)
     bias_part = torch.empty(chunks * nn_, dtype=torch.float32, device=x.device)
     dw = torch.empty((nn_, k), dtype=torch.float32, device=x.device)
@@ -261,7 +217,3 @@ def linear_wgrad_bias(x, gy):
     launch(lib.transoar_linear_wgrad_bias, x, gy.data_ptr(), x.data_ptr(), part.data_ptr(), dw.data_ptr(), bias_part.data_ptr(),
            db.data_ptr(), t, k, nn_, chunks)
     return dw, db
-
-
-def supported(cin, cout, rows):
-    return cin % 8 == 0 and cout % 8 == 0 and cin >= 8 and rows < (1 << 21)
