@@ -37,6 +37,7 @@ LIBS = {
     "libtransoar_augment.so": ["augment.hip"],
     "libtransoar_resize.so": ["resize.hip"],
     "libtransoar_denseattn.so": ["dense_attn.hip"],
+    "libtransoar_patchmerge.so": ["patch_merge.hip"],
 }
 # per-library flags on top of COMMON_FLAGS
 EXTRA_FLAGS = {

@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import rows, win_attn
+from . import instnorm, rows, shadow, win_attn
 from . import tokens as fused_tokens
 from .token_linear import gelu_mlp, gelu_mlp_usable, token_linear
 
@@ -364,8 +364,20 @@ class ConvPatchMerging(nn.Module):
         self._reduction = nn.Sequential(
             nn.Conv3d(dim, dim * 2, kernel_size=2, stride=2, padding=0, bias=bias),
             nn.InstanceNorm3d(dim * 2, affine=affine, eps=eps), nn.ReLU(inplace=True))
+        # bound here, not at the top of the file: a model without this module loads exactly the libraries it loaded before;
+        # one with it fails at construction when libtransoar_patchmerge.so is not built
+        from . import patch_merge  # noqa: F401
 
     def forward(self, x):
+        from . import patch_merge
+        conv, norm = self._reduction[0], self._reduction[1]
+        if (_fast(x) and norm.affine and not norm.track_running_stats and patch_merge.usable(x, conv)
+                and instnorm.supported(x.permute(0, 4, 1, 2, 3), 2 * x.shape[-1])):
+            # the convolution on the token map as it lies (patch_merge.hip), then the fused InstanceNorm + ReLU on the
+            # channels-last view of its result: no permute copies, no MIOpen
+            y = patch_merge.patch_merge_conv(x, conv.weight, shadow.bf16(conv.weight))
+            y = instnorm.instance_norm_relu(y.permute(0, 4, 1, 2, 3), norm.weight, norm.bias, norm.eps)
+            return y.permute(0, 2, 3, 4, 1)
         return self._reduction(x.permute(0, 4, 1, 2, 3)).permute(0, 2, 3, 4, 1)
 
 
